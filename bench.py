@@ -2,7 +2,8 @@
 """Headline benchmark: images/sec of one full reg_transformer train step (train.py:136-209 of the
 reference: [input pipeline,] forward, loss, backward, [gradient all-reduce], Adam) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config resnet50|hrnet_w32|performer]
+    python bench.py --gpus N --steps K --warmup W [--config resnet50|hrnet_w32|performer] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +14,12 @@ network's only legal geometry 224x224 (dataset/load_STB.py:4
 ``value`` = images / wall time of the K steps between the two barriers; the median of the per-step HIP-event
 times is reported beside it.  ``--config hrnet_w32`` / ``performer`` time BASELINE configs[3] / configs[4] on the same
 contract.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds what the headline does not
+need: the instrumented per-kernel roofline step, the CPU-oracle baseline, the hardware-queue sharing probe and the
+data-parallel evidence.  ``--dump-outputs DIR`` writes what the last timed step returned (loss, its parts, the
+pose-length term, the prediction) as DIR/<name>.npy; inputs and weights are seeded, so two builds given the same
+arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -322,6 +329,17 @@ def kernel_rooflines(step, u8, lab):
     return roof, roof_hbm, table
 
 
+def dump_outputs(outdir, loss, parts, lpl, pred):
+    """What a caller of the timed step receives from its last call, as float32 / float64 .npy files."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in (("loss", loss), ("loss_parts", parts), ("pose_length", lpl), ("pred", pred)):
+        if t is None:
+            continue
+        a = t.detach().cpu()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        np.save(os.path.join(outdir, name + ".npy"), a.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -330,9 +348,13 @@ def main():
     ap.add_argument("--batch", type=int, default=96, help="per-GPU batch (reference: 96, script/ablation_pose.sh:11)")
     ap.add_argument("--config", default="resnet50", choices=sorted(GF_TRAIN_PER_IMG),
                     help="resnet50 = BASELINE configs[1]/[2] (the headline); hrnet_w32 = configs[3]; performer = configs[4]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true", help="also run the legs the headline does not need: per-kernel "
+                    "roofline step, CPU-oracle baseline, hardware-queue sharing probe, data-parallel evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline step")
+    ap.add_argument("--kernel-table", action="store_true", help="also print the per-kernel table to stderr (runs the "
+                    "roofline step)")
     ap.add_argument("--h2d", action="store_true", help="also time the steps with the source batch coming from pinned "
                     "host memory (double-buffered H2D; reported as config.pcie_inclusive, never as value)")
     a = ap.parse_args()
@@ -391,28 +413,35 @@ def main():
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
     med = statistics.median(per_step)
     final_loss = float(loss.item())
-    note(f"{a.steps} steps in {dt:.3f} s = {a.batch * world * a.steps / dt:.1f} img/s (median step {med:.3f} ms); "
-         "roofline + CPU baseline legs")
+    note(f"{a.steps} steps in {dt:.3f} s = {a.batch * world * a.steps / dt:.1f} img/s (median step {med:.3f} ms)")
+    if a.dump_outputs and rank == 0:
+        # before any other leg runs a step: the returned tensors may live in buffers the next step reuses
+        dump_outputs(a.dump_outputs, loss, parts, lpl, pred)
 
     pcie = h2d_pipeline_rate(step, u8, lab, a.steps) if a.h2d else None
     roof, roof_hbm, table = None, None, {}
-    if not a.no_roofline:
+    if (a.full and not a.no_roofline) or a.kernel_table:
         # every rank runs the instrumented step (it contains the gradient all-reduces); rank 0 reports
+        note("roofline leg")
         roof, roof_hbm, table = kernel_rooflines(step, u8, lab)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "resnet50":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == "resnet50":
+        note("CPU baseline leg")
         cpu = cpu_baseline()
 
     # which side streams of the step share a hardware queue on this rank (scat_amd/streams.py; ~20 ms of spin kernels,
     # after everything that is timed): evidence that the queue plan held where the step actually ran
     from scat_amd import streams
-    queue_mates = ["+".join((x, y)) + (" (one stream)" if why == "same stream" else "") for x, y, why in streams.sharing(dev)]
+    queue_mates = None
+    if a.full:
+        queue_mates = ["+".join((x, y)) + (" (one stream)" if why == "same stream" else "")
+                       for x, y, why in streams.sharing(dev)]
     # data-parallel evidence, so that a scaling record can be audited for "did the collectives see N ranks, on which
     # queues": per rank the queue-mates and what the queue-plan verification found; the backend, its version, whether
     # ReduceOp.AVG is native, and the bytes of every gradient bucket
     dp_info = None
     buckets = step.ts.buckets if step.ts is not None else getattr(step.opt, "buckets", None)
-    if world > 1 or dist.is_initialized():
+    if a.full and (world > 1 or dist.is_initialized()):
         mine = {"rank": rank, "hw_queue_mates": queue_mates, "queue_plan": streams.plan_report(dev)}
         per_rank = [None] * world
         if world > 1:

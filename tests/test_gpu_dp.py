@@ -289,7 +289,7 @@ def test_bench_two_ranks_through_the_launcher():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -580,14 +580,19 @@ def test_bottleneck_golden(golden, math):
         ops.set_math_mode(saved)
 
 
-def test_layer4_standalone_on_7x7_maps():
+def test_layer4_standalone_on_7x7_maps(monkeypatch):
     """``net.layer4(x)`` taken out of the network, train mode, forward + backward (models/resnet.py:78-98, 125-140): its
     block outputs are 7x7 maps, which the 1-bit sign mask cannot pack (H*W % 4 != 0) — the stand-alone block node
     must then keep the output for the ReLU sign of ``relu(bn3(.) + residual)`` instead of deriving it from bn3 alone
-    (a wrong sign mask is an O(1) error).  Against the oracle's three Bottlenecks in fp64, with the
-    oracle in fp32 as the yardstick: nine batch-statistics BatchNorms over 392 samples and the ReLUs between them make
-    these gradients ill conditioned (the CPU fp32 evaluation itself is ~1 % from fp64), so the HIP gradients must be as
-    close to fp64 as the CPU fp32 ones are (3x + 2e-4), the forward within 2e-5."""
+    (a wrong sign mask is an O(1) error).  Against the oracle's three Bottlenecks in fp64, made tight the
+    way test_bottleneck_batch96_against_fp64 is: nine batch-statistics BatchNorms over 392 samples and the ReLUs
+    between them flip a few elements within one fp32 rounding of zero in any fp32 evaluation, each an O(1) change of
+    the gradient there (the CPU oracle in fp32 is 0.4-1 % from fp64 on dx, depending on the CPU it runs on, so it
+    cannot serve as the yardstick).  So: the forward within 2e-5 of plain fp64; the HIP run's ReLU sign patterns
+    (bn1 / bn2: sign of fma(c, scale, shift) as the kernels form it; block output: its sign) disagree with fp64's
+    only within 2e-5 of zero and in fewer than 2e-5 of the elements; every gradient within 5e-5 of fp64 evaluated
+    with those sign patterns."""
+    import torch.nn.functional as F
     from scat_amd.models import resnet as R
 
     net = R.resnet50(pretrained=False, num_classes=512)
@@ -598,34 +603,72 @@ def test_layer4_standalone_on_7x7_maps():
     x = T(synth.normal_like(43, "x3", (B, 1024, 14, 14))).abs_()       # (a block input is a ReLU output)
     cot = T(synth.normal_like(44, "cot4", (B, 2048, 7, 7)))
 
-    def oracle(dt, blocks, xin, prefix):
-        sd = {k[len(prefix):]: (v.detach().clone().to(dt) if v.is_floating_point() else v.clone())
-              for k, v in full.items() if k.startswith(prefix)}
-        for k, v in sd.items():
-            if v.is_floating_point() and "running" not in k:
-                v.requires_grad_(True)
-        xr = xin.detach().clone().to(dt).requires_grad_(True)
+    # the sign patterns of every block forward the module path runs, read off its tape as the forward leaves it
+    signs = []
+    block_forward = R._block_forward
+
+    def recording(blk, xin, training, wp=None):
+        rec = block_forward(blk, xin, training, wp)
+        _, _, c1, s1, c2, s2 = rec[:6]
+        signs.append(tuple(m.cpu() for m in (
+            c1.double() * s1.scale.double().view(1, -1, 1, 1) + s1.shift.double().view(1, -1, 1, 1) > 0,
+            c2.double() * s2.scale.double().view(1, -1, 1, 1) + s2.shift.double().view(1, -1, 1, 1) > 0,
+            rec[10] > 0)))
+        return rec
+
+    monkeypatch.setattr(R, "_block_forward", recording)
+
+    def state():
+        return {k[len("layer4."):]: (v.detach().clone().double() if v.is_floating_point() else v.clone())
+                for k, v in full.items() if k.startswith("layer4.")}
+
+    def block64(sd, key, xin, stride, masks=None):
+        """one Bottleneck in fp64: its own ReLUs (masks None) or relu(z) -> z * mask; -> (output, pre-activations)"""
+        def bn(k, t):
+            return O.batch_norm(sd, key + "." + k, t, True)
+
+        act = (lambda z, i: F.relu(z)) if masks is None else (lambda z, i: z * masks[i])
+        z1 = bn("bn1", F.conv2d(xin, sd[key + ".conv1.weight"]))
+        z2 = bn("bn2", F.conv2d(act(z1, 0), sd[key + ".conv2.weight"], stride=stride, padding=1))
+        z3 = bn("bn3", F.conv2d(act(z2, 1), sd[key + ".conv3.weight"]))
+        res = xin
+        if key + ".downsample.0.weight" in sd:
+            res = bn("downsample.1", F.conv2d(xin, sd[key + ".downsample.0.weight"], stride=stride))
+        z3 = z3 + res
+        return act(z3, 2), (z1, z2, z3)
+
+    def held(blocks, xin, got_y, got_dx, got_p, masks, what):
+        sd = state()
+        with torch.no_grad():
+            y = xin.double()
+            for (key, stride), m in zip(blocks, masks):
+                y, zs = block64(sd, key, y, stride)
+                for name, z, mm in zip(("bn1", "bn2", "out"), zs, m):
+                    bad = (z > 0) != mm
+                    nbad = int(bad.sum())
+                    worst = float(z[bad].abs().max() / z.abs().max()) if nbad else 0.0
+                    assert nbad <= 2e-5 * z.numel() and worst < 2e-5, (what, key, name, nbad, z.numel(), worst)
+        assert rel_err(got_y, y) < 2e-5, (what, rel_err(got_y, y))
+        sd = state()
+        leaves = {k: v.requires_grad_(True) for k, v in sd.items() if v.is_floating_point() and "running" not in k}
+        xr = xin.detach().clone().double().requires_grad_(True)
         yr = xr
-        for key, stride in blocks:
-            yr = O.bottleneck(sd, key, yr, stride, True)
-        (yr * cot.to(dt)).sum().backward()
-        return yr.detach(), xr.grad, {k: v.grad for k, v in sd.items() if v.is_floating_point() and v.grad is not None}
+        for (key, stride), m in zip(blocks, masks):
+            yr, _ = block64(sd, key, yr, stride, m)
+        (yr * cot.double()).sum().backward()
+        rows = {"dx": rel_err(got_dx, xr.grad)}
+        rows.update({k: rel_err(got_p[k], v.grad) for k, v in leaves.items() if v.grad is not None})
+        assert len(rows) == 1 + len(got_p), (what, sorted(set(got_p) - set(rows)))
+        worst = max(rows, key=rows.get)
+        print(f"{what}: worst gradient {worst} {rows[worst]:.2e} vs fp64 with the run's sign patterns")
+        assert rows[worst] < 5e-5, (what, worst, rows)
 
-    def held(got_x, got_p, r32, r64, what):
-        e_h, e_c = rel_err(got_x, r64[1]), rel_err(r32[1], r64[1])
-        assert e_h <= 3 * e_c + 2e-4, (what, "dx", e_h, e_c)
-        eh = np.array([rel_err(got_p[k], r64[2][k]) for k in r64[2]])
-        ec = np.array([rel_err(r32[2][k], r64[2][k]) for k in r64[2]])
-        assert np.median(eh) <= 2 * np.median(ec) + 2e-4 and eh.max() <= 3 * ec.max() + 2e-4, (what, eh.max(), ec.max())
-
-    blocks = (("0", 2), ("1", 1), ("2", 1))
-    r32, r64 = oracle(torch.float32, blocks, x, "layer4."), oracle(torch.float64, blocks, x, "layer4.")
     xg = x.cuda().requires_grad_(True)
     y = layer4(xg)
-    assert tuple(y.shape) == (B, 2048, 7, 7)
-    assert rel_err(y, r64[0]) < 2e-5
+    assert tuple(y.shape) == (B, 2048, 7, 7) and len(signs) == 3
     (y * cot.cuda()).sum().backward()
-    held(xg.grad, {k: p.grad for k, p in layer4.named_parameters()}, r32, r64, "layer4")
+    held((("0", 2), ("1", 1), ("2", 1)), x, y, xg.grad, {k: p.grad for k, p in layer4.named_parameters()}, signs,
+         "layer4")
     # one block alone, no shortcut convolution (the residual is the block input itself)
     blk = layer4[2]
     xin = y.detach().cpu()
@@ -633,10 +676,9 @@ def test_layer4_standalone_on_7x7_maps():
     for p in blk.parameters():
         p.grad = None
     yb = blk(xb)
+    assert len(signs) == 4
     (yb * cot.cuda()).sum().backward()
-    b32, b64 = oracle(torch.float32, (("2", 1),), xin, "layer4."), oracle(torch.float64, (("2", 1),), xin, "layer4.")
-    assert rel_err(yb, b64[0]) < 2e-5
-    held(xb.grad, {"2." + k: p.grad for k, p in blk.named_parameters()}, b32, b64, "layer4.2")
+    held((("2", 1),), xin, yb, xb.grad, {"2." + k: p.grad for k, p in blk.named_parameters()}, signs[3:], "layer4.2")
 
 
 @pytest.mark.timeout(1700)

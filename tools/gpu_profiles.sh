@@ -8,10 +8,10 @@ R=${1:-r03}
 export TMPDIR=/tmp
 B="python3 $GRAFT_REPO_ROOT/bench.py"
 # 1. bench lines
-timeout -k 10 400 python bench.py --h2d > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err; echo "bench rc=$?"
-timeout -k 10 300 python bench.py --config hrnet_w32 --steps 20 --warmup 5 > $O/${R}_bench_line_hrnet_w32.json 2>/dev/null
-timeout -k 10 300 python bench.py --config performer --steps 30 --warmup 8 > $O/${R}_bench_line_performer.json 2>/dev/null
-SCAT_MATH=f32 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $O/${R}_bench_line_f32mfma.json 2>/dev/null
+timeout -k 10 400 python bench.py --full --h2d > $O/${R}_bench_line.json 2> $O/${R}_bench_line.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --config hrnet_w32 --steps 20 --warmup 5 > $O/${R}_bench_line_hrnet_w32.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --config performer --steps 30 --warmup 8 > $O/${R}_bench_line_performer.json 2>/dev/null
+SCAT_MATH=f32 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $O/${R}_bench_line_f32mfma.json 2>/dev/null
 echo "bench lines done"; cut -c1-200 $O/${R}_bench_line.json
 echo "[profiles] kernel stats"
 prof() {

@@ -14,4 +14,4 @@ tools/pmc_run.sh $O/pmc_calib "FETCH_SIZE" -- python3 tools/fetch_calib.py > $O/
 python3 tools/fetch_calib.py --report $O/pmc_calib/run_counter_collection.csv > $O/r04_fetch_calib.txt 2>&1; cat $O/r04_fetch_calib.txt
 rm -rf $O/pmc_calib
 echo "[hrnet bench]"
-timeout -k 10 300 python bench.py --config hrnet_w32 --steps 20 --warmup 5 --no-cpu-baseline > $O/r04_bench_line_hrnet_w32_a.json 2>/dev/null; cut -c1-150 $O/r04_bench_line_hrnet_w32_a.json
+timeout -k 10 300 python bench.py --full --config hrnet_w32 --steps 20 --warmup 5 --no-cpu-baseline > $O/r04_bench_line_hrnet_w32_a.json 2>/dev/null; cut -c1-150 $O/r04_bench_line_hrnet_w32_a.json
