@@ -1,6 +1,7 @@
 """Per-kernel parity on a real MI355X: every C-ABI op against the plain PyTorch fp32/fp64 CPU op
 it replaces, on seeded inputs. Tolerance (norm-wise relative, max|a-b|/max|b|): 2e-5 for
 contractions (fp32 fma chains in a different order), 1e-5 for element-wise / normalisation."""
+import math
 import os
 
 import numpy as np
@@ -1511,3 +1512,264 @@ def test_bn_backward_sums_in_the_data_gradient_epilogue(ops, B, C, K, H):
     # the arm is one-shot: the next call is the plain accumulate again
     again = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True)
     assert ops.epilogue_bnb_groups() == 0 and not torch.equal(again, ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# HRNet-W32 (c = 32, 224 x 224; BASELINE configs[3]) at the benchmarked batch 96: every convolution geometry of the
+# backbone except layer1's four Bottlenecks (ResNet's block executor, in CONVS above), plus the wrapper's 3x3/2 512->128
+# reduction on the 28x28 view (models/hand_net.py EncoderTransformerHRNet).  Each geometry runs the way the step runs it:
+#   "cbr"  : hrnet._CbrFn — forward with the BatchNorm sums, taken about a stats_shift, in its epilogue; the BN finish; dW; dX
+#   "block": hrnet._BasicBlockFn — conv1 forward; conv2 forward and dW with bn1 + ReLU in the operand load; dW plain;
+#            dX plain (conv2) and accumulating onto the residual gradient (conv1)
+#   "plain": snn.Conv2d — forward, dW, dX (the exchange's 1x1s, the last 3x3/2 of each strided chain, the wrapper's reduction)
+#   "bias" : snn.Conv2d with a bias — final_layer (forward + bias, the bias gradient's column sum)
+# tests/test_hrnet_geometry.py holds the table to the oracle's HRNet-W32: every geometry it runs is here or in CONVS.
+HRNET_B96 = {
+    # (Cin, Cout, k, stride, H = W of the input): roles
+    (3, 64, 3, 2, 224): ("cbr",), (64, 64, 3, 2, 112): ("cbr",), (256, 32, 3, 1, 56): ("cbr",),
+    (256, 64, 3, 2, 56): ("cbr",), (32, 32, 3, 2, 56): ("cbr",), (32, 32, 3, 2, 28): ("cbr",),
+    (64, 64, 3, 2, 28): ("cbr",), (64, 128, 3, 2, 28): ("cbr", "plain"), (128, 256, 3, 2, 14): ("cbr", "plain"),
+    (32, 32, 3, 1, 56): ("block",), (64, 64, 3, 1, 28): ("block",), (128, 128, 3, 1, 14): ("block",),
+    (256, 256, 3, 1, 7): ("block",),
+    (32, 64, 3, 2, 56): ("plain",), (32, 128, 3, 2, 28): ("plain",), (32, 256, 3, 2, 14): ("plain",),
+    (64, 256, 3, 2, 14): ("plain",), (64, 32, 1, 1, 28): ("plain",), (128, 32, 1, 1, 14): ("plain",),
+    (128, 64, 1, 1, 14): ("plain",), (256, 32, 1, 1, 7): ("plain",), (256, 64, 1, 1, 7): ("plain",),
+    (256, 128, 1, 1, 7): ("plain",), (32, 128, 1, 1, 56): ("bias",),
+    (512, 128, 3, 2, 28): ("plain",),      # the wrapper's conv1x1_channel_reduction (a 3x3/2 despite its name)
+}
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("cin,cout,k,s,H", sorted(HRNET_B96))
+def test_hrnet_conv_batch96_instantiations(ops, cin, cout, k, s, H):
+    B, p = 96, k // 2
+    roles = HRNET_B96[(cin, cout, k, s, H)]
+    name = f"hrnet {cin}->{cout} k{k} s{s} {H}x{H}"
+    gen = torch.Generator().manual_seed(3000 + cin + 7 * cout + 31 * k + 5 * s + H)
+    z = torch.randn((B, cin, H, H), generator=gen)
+    # what the step feeds it: the image (stem) or a ReLU output (every other plain read); "block" also reads z raw
+    x = z * 0.5 + 0.1 if cin == 3 else F.relu(z)
+    w = torch.randn((cout, cin, k, k), generator=gen) * (2.0 / (cin * k * k)) ** 0.5
+    bias = torch.randn((cout,), generator=gen) * 0.2
+    x64 = x.double().requires_grad_(True)
+    w64 = w.double().requires_grad_(True)
+    y = F.conv2d(x64, w64, stride=s, padding=p)
+    dy = torch.randn(tuple(y.shape), generator=gen)
+    dx_ref, dw_ref = torch.autograd.grad(y, (x64, w64), dy.double())
+    y = y.detach()
+    xg, wg, dyg = g(x), g(w), g(dy)
+    wp = ops.WeightPrep()          # prepared weights like the network's: first call registers, run() re-lays, then w_ready=1
+
+    def prepared(fn):
+        fn()
+        wp.run(True)
+        return fn()
+
+    if "cbr" in roles:
+        # the BatchNorm sums about the previous step's batch mean (resnet._BNState leaves it in bn._stat_ref)
+        mean64, var64 = y.mean(dim=(0, 2, 3)), y.var(dim=(0, 2, 3), unbiased=False)
+        shift = g((mean64 + 0.05 * var64.sqrt() * torch.randn((cout,), generator=gen).double()).float())
+        yg = prepared(lambda: ops.conv2d_fwd(xg, wg, s, p, wp=wp, stats=True, stats_shift=shift))
+        _b96_note(f"{name} fwd_stats", _label(ops))
+        assert rel_err(yg, y) < 2e-5
+        had_partials = getattr(yg, "scat_stats", None) is not None
+        gamma, beta = g(torch.rand((cout,), generator=gen) + 0.5), g(torch.rand((cout,), generator=gen) - 0.5)
+        rm, rv = torch.zeros(cout, device=DEV), torch.ones(cout, device=DEV)
+        mean, invstd, scale, bshift = ops.bn_train_stats(yg, gamma, beta, rm, rv)
+        assert rel_err(mean, mean64) < 2e-5, had_partials
+        assert rel_err(invstd, (var64 + 1e-5).rsqrt()) < 2e-5, had_partials
+        assert rel_err(rv, 0.9 + 0.1 * y.var(dim=(0, 2, 3), unbiased=True)) < 2e-5, had_partials
+        del yg
+    if "plain" in roles or "block" in roles:
+        yg = prepared(lambda: ops.conv2d_fwd(xg, wg, s, p, wp=wp))
+        _b96_note(f"{name} fwd", _label(ops))
+        assert rel_err(yg, y) < 2e-5
+        del yg
+    if "bias" in roles:
+        yb = prepared(lambda: ops.conv2d_fwd(xg, wg, s, p, bias=g(bias), wp=wp))
+        _b96_note(f"{name} fwd_bias", _label(ops))
+        assert rel_err(yb, y + bias.double().view(1, -1, 1, 1)) < 2e-5
+        del yb
+        db = ops.colsum(dyg.permute(0, 2, 3, 1).reshape(-1, cout).contiguous())
+        assert rel_err(db, dy.double().sum(dim=(0, 2, 3))) < 1e-5
+
+    dwg = ops.conv2d_wgrad(dyg, xg, tuple(w.shape), s, p)
+    _b96_note(f"{name} wgrad", _label(ops))
+    assert rel_err(dwg, dw_ref) < 2e-5
+    del dwg
+    if cin != 3:                   # (the image needs no gradient)
+        dxg = prepared(lambda: ops.conv2d_dgrad_w(dyg, wg, tuple(x.shape), s, p, wp=wp))
+        _b96_note(f"{name} dgrad", _label(ops))
+        assert rel_err(dxg, dx_ref) < 2e-5
+        del dxg
+
+    if "block" in roles:
+        # conv2 reads relu(bn1(c1)) formed in its operand load, forward and for dW
+        sc = torch.rand((cin,), generator=gen) + 0.5
+        sh = torch.rand((cin,), generator=gen) - 0.5
+        a64 = F.relu(z.double() * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1))
+        ya = F.conv2d(a64, w.double(), stride=s, padding=p)
+        dwa_ref = torch.nn.grad.conv2d_weight(a64, tuple(w.shape), dy.double(), stride=s, padding=p)
+        zg, tfa = g(z), (g(sc), g(sh), True)
+        yt = prepared(lambda: ops.conv2d_fwd(zg, wg, s, p, *tfa, wp=wp))
+        _b96_note(f"{name} fwd_tf", _label(ops))
+        assert rel_err(yt, ya.detach()) < 2e-5
+        del yt
+        dwt = ops.conv2d_wgrad(dyg, zg, tuple(w.shape), s, p, *tfa)
+        _b96_note(f"{name} wgrad_tf", _label(ops))
+        assert rel_err(dwt, dwa_ref) < 2e-5
+        del dwt
+        # conv1's data gradient accumulates straight into the residual gradient
+        base = torch.randn(tuple(x.shape), generator=gen)
+        dxa = ops.conv2d_dgrad_w(dyg, wg, tuple(x.shape), s, p, out=g(base), accumulate=True, wp=wp)
+        _b96_note(f"{name} dgrad_acc", _label(ops))
+        assert rel_err(dxa, dx_ref + base.double()) < 2e-5
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# FAVOR+ core (csrc/performer.hip) against the fp64 formula of oracle.performer_block (prm_exp, D, kptv), forward, the
+# saved tensors and the backward, at the performer config's shape (B = 96, T = 21 tokens, 16 heads of e = 49, m = 24) and
+# at the kernels' edges: m = 64 / 65 / 128 (the lane loops and performer_bwd3_kernel's sh[4][2][128] LDS bound), e > 64,
+# T = 1, and a B*H*T that is not a multiple of 4 (a dead wave in the last workgroup of bwd1 / bwd3 / out).
+def _favor64(kqv, w):
+    """kqv[B,T,H,3e] (k | q | v), w[m,e] -> y[B,T,H*e], kp, qp [B,H,T,m], kptv [B,H,e,m], ksum [B,H,m], D [B,H,T]"""
+    B, T, H, e3 = kqv.shape
+    e, m = e3 // 3, w.shape[0]
+    k, q, v = (t.permute(0, 2, 1, 3) for t in kqv.split(e, dim=-1))        # [B,H,T,e]
+
+    def prm_exp(t):
+        return torch.exp(t @ w.t() - (t * t).sum(dim=-1, keepdim=True) / 2) / math.sqrt(m)
+
+    kp, qp = prm_exp(k), prm_exp(q)
+    ksum = kp.sum(dim=2)
+    D = (qp * ksum.unsqueeze(2)).sum(dim=-1)
+    kptv = torch.einsum("bhtn,bhtm->bhnm", v, kp)
+    y = torch.einsum("bhtm,bhnm->bhtn", qp, kptv) / D.unsqueeze(-1)
+    return y.permute(0, 2, 1, 3).reshape(B, T, H * e), kp, qp, kptv, ksum, D
+
+
+@pytest.mark.parametrize("B,T,H,e,m", [(96, 21, 16, 49, 24), (3, 21, 16, 49, 64), (2, 21, 8, 49, 65), (2, 21, 4, 49, 128),
+                                       (2, 9, 3, 100, 24), (3, 5, 2, 130, 65), (5, 1, 4, 49, 24), (3, 7, 5, 49, 24),
+                                       (1, 3, 1, 70, 128)])
+def test_performer_core(ops, B, T, H, e, m):
+    gen = torch.Generator().manual_seed(4000 + B + 3 * T + 5 * H + 7 * e + 11 * m)
+    kqv = torch.randn((B, T, H, 3 * e), generator=gen) * (1.5 / e ** 0.5)
+    w = torch.randn((m, e), generator=gen)
+    k64 = kqv.double().requires_grad_(True)
+    y64, kp, qp, kptv, ksum, D = _favor64(k64, w.double())
+    dy = torch.randn(tuple(y64.shape), generator=gen)
+    (dk_ref,) = torch.autograd.grad(y64, (k64,), dy.double())
+    yg, saved = ops.performer_fwd(g(kqv), g(w), H)
+    assert rel_err(yg, y64) < 2e-5
+    for got, ref in zip(saved, (kp, qp, kptv, ksum, D)):
+        assert rel_err(got, ref) < 2e-5
+    dkg = ops.performer_bwd(g(dy), g(kqv), g(w), yg, saved)
+    for sl in range(3):            # k, q, v slices on their own: each has its own formula in performer_bwd3_kernel
+        got, ref = dkg[..., sl * e:(sl + 1) * e], dk_ref[..., sl * e:(sl + 1) * e]
+        if T == 1 and sl < 2:      # one token: y = v whatever k and q are, so dk = dq = 0 up to rounding (of dv's size)
+            assert float((got.cpu().double() - ref).abs().max()) < 2e-5 * float(dk_ref.abs().max()), "kqv"[sl]
+        else:
+            assert rel_err(got, ref) < 2e-5, "kqv"[sl]
+
+
+def test_performer_core_rejects_m_above_128(ops):
+    from scat_amd._lib import ScatError
+
+    kqv, w = torch.zeros((1, 2, 1, 3 * 8), device=DEV), torch.zeros((129, 8), device=DEV)
+    with pytest.raises(ScatError, match="m <= 128"):
+        ops.performer_fwd(kqv, w, 1)
+    y, saved = ops.performer_fwd(kqv, w[:128].contiguous(), 1)
+    with pytest.raises(ScatError, match="m <= 128"):
+        ops.performer_bwd(torch.zeros_like(y), kqv, w, y, saved)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The small ops of the HRNet exchange, the HRNet wrapper and the performer's train mode, on their own.
+@pytest.mark.parametrize("B,C,H,W,f", [(2, 3, 7, 5, 2), (3, 4, 8, 6, 2), (2, 3, 7, 5, 4), (1, 5, 4, 6, 4), (2, 3, 3, 5, 8),
+                                       (1, 2, 2, 2, 8), (1, 1, 1, 1, 2),
+                                       # the HRNet-W32 exchange at batch 96: 2^(j-i) onto the 56 / 28 / 14 maps
+                                       (96, 32, 28, 28, 2), (96, 32, 14, 14, 4), (96, 32, 7, 7, 8), (96, 64, 14, 14, 2),
+                                       (96, 64, 7, 7, 4), (96, 128, 7, 7, 2)])
+def test_upsample_nearest(ops, B, C, H, W, f):
+    gen = torch.Generator().manual_seed(5000 + B + C + H * W + f)
+    x = torch.randn((B, C, H, W), generator=gen)
+    dy = torch.randn((B, C, H * f, W * f), generator=gen)
+    y = ops.upsample_nearest_fwd(g(x), f)
+    assert torch.equal(y.cpu(), F.interpolate(x, scale_factor=float(f), mode="nearest"))
+    ref = dy.double().reshape(B, C, H, f, W, f).sum(dim=(3, 5))          # the f x f block sums
+    assert rel_err(ops.upsample_nearest_bwd(g(dy), f), ref) < 1e-5
+
+
+@pytest.mark.parametrize("B,T,D", [(96, 128, 196), (96, 22, 784), (3, 7, 5), (2, 1, 61), (5, 33, 1), (4, 129, 197)])
+def test_token_mean(ops, B, T, D):
+    gen = torch.Generator().manual_seed(5100 + B + T + D)
+    x = torch.randn((B, T, D), generator=gen) + 0.5
+    dy = torch.randn((B, D), generator=gen)
+    assert rel_err(ops.token_mean_fwd(g(x)), x.double().mean(dim=1)) < 1e-5
+    dx = ops.token_mean_bwd(g(dy), T)
+    assert tuple(dx.shape) == (B, T, D)
+    assert rel_err(dx, (dy.double() / T).unsqueeze(1).expand(B, T, D)) < 1e-6
+
+
+@pytest.mark.parametrize("n,p", [(96 * 21 * 784, 0.1), (100003, 0.1), (1023, 0.5), (7, 0.1), (1, 0.3), (4099, 0.0),
+                                 (96 * 21 * 3136, 0.1)])
+def test_dropout(ops, n, p):
+    """the keep mask is oracle.hash_dropout_mask element for element, kept values scale by 1/(1-p) (in fp32, as
+    scat_dropout forms it), and snn.Dropout's backward applies the same mask"""
+    import random
+
+    from oracle.scat_oracle import hash_dropout_mask
+    from scat_amd import nn as snn
+
+    gen = torch.Generator().manual_seed(5200 + n)
+    x = torch.randn((n,), generator=gen) + 0.01          # (no exact zeros: a zero output then means "dropped")
+    dy = torch.randn((n,), generator=gen)
+    seed = random.Random(n).getrandbits(63)
+    keep = hash_dropout_mask(n, p, seed)
+    scale = torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(p, dtype=torch.float32))
+    y = ops.dropout(g(x), p, seed).cpu()
+    assert torch.equal((y != 0).double(), keep)
+    assert torch.equal(y, x * keep.float() * scale)
+    assert rel_err(y, x.double() * keep / (1.0 - p)) < 1e-6
+    if 0 < p and n > 1000:
+        assert abs(1.0 - keep.mean().item() - p) < 6 * (p * (1 - p) / n) ** 0.5
+    # through the module: the seed is drawn from python random at forward, the backward regenerates the same mask
+    mod = snn.Dropout(p).train()
+    xg = g(x).requires_grad_(True)
+    random.seed(n)
+    yg = mod(xg)
+    random.seed(n)
+    keep2 = hash_dropout_mask(n, p, random.getrandbits(63)) if p > 0 else torch.ones(n, dtype=torch.float64)
+    yg.backward(g(dy))
+    assert torch.equal(yg.detach().cpu(), x * keep2.float() * scale)
+    assert torch.equal(xg.grad.cpu(), dy * keep2.float() * scale)
+
+
+# The HRNet wrapper's transformer at batch 96 runs on 96 x 128 = 12 288 tokens: the qkv projection (12 288 x 1 536 x 196)
+# and its weight / data gradients cross GEMM_SPLIT_MIN and run on scat_gemm_split, the output and MLP projections stay on
+# the fp32 engine — at a row count no other test uses.
+@pytest.mark.parametrize("N,K,has_bias", [(1536, 196, False), (196, 512, True), (392, 196, True), (196, 392, True)])
+def test_linear_hrnet_wrapper_tokens(ops, N, K, has_bias):
+    M = 96 * 128
+    gen = torch.Generator().manual_seed(5300 + N + K)
+    x = torch.randn((M, K), generator=gen)
+    w = torch.randn((N, K), generator=gen) * K ** -0.5
+    b = torch.randn((N,), generator=gen) if has_bias else None
+    dy = torch.randn((M, N), generator=gen)
+    x64, w64 = x.double(), w.double()
+    y = x64 @ w64.t() + (b.double() if has_bias else 0.0)
+
+    def on_split(m, n, k):
+        ok = ops._gemm_split_ok(m, n, k)
+        assert ("gemm_split" in _label(ops)) == ok, (_label(ops), m, n, k)
+        return ok
+
+    assert rel_err(ops.linear_fwd(g(x), g(w), g(b) if has_bias else None), y) < 2e-5
+    split = [on_split(M, N, K)]
+    assert rel_err(ops.linear_dgrad(g(dy), g(w)), dy.double() @ w64) < 2e-5
+    split.append(on_split(M, K, N))
+    assert rel_err(ops.linear_wgrad(g(dy), g(x)), dy.double().t() @ x64) < 2e-5
+    split.append(on_split(N, K, M))
+    assert rel_err(ops.colsum(g(dy)), dy.double().sum(0)) < 1e-5
+    # the qkv projection is the one that crosses the threshold (in the default product mode)
+    assert all(split) == (N == 1536 and ops.get_math_mode() == 1 and ops.GEMM_SPLIT), split
