@@ -373,6 +373,24 @@ int scat_tokens_bwd(const float* dy, const int32_t* masked, int nmasked, float* 
  * (hwc = 1: [B,SH,SW,3] as decoded; 0: [B,3,SH,SW]) -> x/127.5-1 -> bilinear (align_corners=False) -> fp32
  * [B,3,OH,OW] in one pass */
 int scat_preprocess_u8(const uint8_t* src, float* dst, int B, int SH, int SW, int OH, int OW, int hwc, void* stream);
+/* sample augmentation on the device, two launches.
+ * scat_augment_plan: the label half of dataset/load_STB.py:98-110 (rescale_3d_joints_flip, if normalize_3d), :69-74
+ * (hand_flip: x = W - x), dataset/rotation.py:11-45 (rotate_img: cv2.getRotationMatrix2D about (W//2, H//2) onto the
+ * enlarged canvas, the 3-D joints rotated about z) and load_STB.py:76-96 (crop_hand), in fp64.  j2d[B,21,2] pixel
+ * coordinates in the un-mirrored W x H frame, j3d[B,21,3]; params[B,4] int32 = (flip 0/1, k: 0 = no blur else 1..10,
+ * vert 0/1, angle: 0 = none else 1..360 degrees) as load_STB.py:265-272 draws them -> labels[B,105] = 63 3-D then 42 2-D
+ * entries (load_STB.py:286-289) and plan[B,24]: per sample six fp64 values (bit patterns in floats 0..11) A00 A01 A02 A10
+ * A11 A12, the map from an output position (p, q) in 224 x 224 to the source point (A00 p + A01 q + A02, A10 p + A11 q +
+ * A12); then as floats L, T, nw, nh (the integer crop box), n (supersampling grid side 1..4), flip, k, vert; 4 zeros.
+ * plan must be 8-byte aligned.
+ * scat_augment_warp_u8: the image half of the same lines (ImageOps.mirror, load_STB.py:154-187 motion_blur's
+ * cv2.filter2D, rotation.py:30 cv2.warpAffine, load_STB.py:85-88 crop + resize) and of :48-67 (ToTensor, Normalize): src
+ * uint8 (hwc = 1: [B,SH,SW,3]; 0: [B,3,SH,SW]), SH, SW >= 11 -> dst[B,3,OH,OW] fp32 in [-1,1]; every output pixel is the
+ * mean of n x n bilinear samples of the mirrored, blurred frame at the plan's map, black outside the frame.  OH = OW = 224. */
+int scat_augment_plan(const float* j2d, const float* j3d, const int32_t* params, float* labels, float* plan, int B, int W,
+                      int H, int normalize_3d, void* stream);
+int scat_augment_warp_u8(const uint8_t* src, const float* plan, float* dst, int B, int SH, int SW, int OH, int OW, int hwc,
+                         void* stream);
 /* nearest-neighbour upsample by an integer factor (models/hrnet.py:107) and mean over tokens
  * (hand_net.py:203 feat.mean(dim=1); vision_performer.py:108) */
 int scat_upsample_nearest_fwd(const float* x, float* y, int B, int C, int H, int W, int factor, void* stream);

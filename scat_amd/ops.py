@@ -1047,6 +1047,43 @@ def preprocess_u8(src, out_hw=(224, 224), hwc=False):
     return dst
 
 
+AUGMENT_PLAN_FLOATS = 24   # floats per sample of the plan record (layout: include/scat_hip.h scat_augment_plan)
+
+
+def augment_plan(j2d, j3d, params, size_wh, normalize_3d=True):
+    """Labels and image plan of a batch of augmented samples (include/scat_hip.h scat_augment_plan): j2d [B,21,2] /
+    j3d [B,21,3] fp32, params [B,4] int32 (flip, k, vert, angle), size_wh = (W, H) of the frames -> (labels [B,105],
+    plan [B,24]), both fp32."""
+    for t, dt, shape in ((j2d, torch.float32, (21, 2)), (j3d, torch.float32, (21, 3)), (params, torch.int32, (4,))):
+        if not t.is_cuda:
+            raise ScatError("augment_plan needs GPU tensors (no CPU fallback on the product path)")
+        if not (t.dtype == dt and t.is_contiguous() and tuple(t.shape[1:]) == shape and t.shape[0] == j2d.shape[0]):
+            raise ScatError(f"augment_plan needs contiguous j2d [B,21,2] fp32, j3d [B,21,3] fp32, params [B,4] int32; got "
+                            f"{t.dtype} {tuple(t.shape)} contiguous={t.is_contiguous()}")
+    B = j2d.shape[0]
+    labels = torch.empty((B, 105), dtype=torch.float32, device=j2d.device)
+    plan = torch.empty((B, AUGMENT_PLAN_FLOATS), dtype=torch.float32, device=j2d.device)
+    lib().scat_augment_plan(_p(j2d), _p(j3d), _p(params), _p(labels), _p(plan), B, int(size_wh[0]), int(size_wh[1]),
+                            int(bool(normalize_3d)), _stream())
+    return labels, plan
+
+
+def augment_warp_u8(src, plan, out_hw=(224, 224), hwc=True):
+    """uint8 frames [B,H,W,3] (or [B,3,H,W] with hwc=False) on the GPU + plan [B,24] -> fp32 [B,3,224,224] in [-1,1]:
+    mirror, motion blur, rotation, crop and resize as one sampling pass (include/scat_hip.h scat_augment_warp_u8)."""
+    if not (src.is_cuda and plan.is_cuda):
+        raise ScatError("augment_warp_u8 needs GPU tensors (no CPU fallback on the product path)")
+    if not (src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 4 and src.shape[3 if hwc else 1] == 3):
+        raise ScatError("augment_warp_u8 needs a contiguous uint8 tensor [B,H,W,3] (hwc) or [B,3,H,W]")
+    B = src.shape[0]
+    if not (plan.dtype == torch.float32 and plan.is_contiguous() and tuple(plan.shape) == (B, AUGMENT_PLAN_FLOATS)):
+        raise ScatError(f"augment_warp_u8 needs a contiguous fp32 plan [{B},{AUGMENT_PLAN_FLOATS}]")
+    SH, SW = (src.shape[1], src.shape[2]) if hwc else (src.shape[2], src.shape[3])
+    dst = torch.empty((B, 3, out_hw[0], out_hw[1]), dtype=torch.float32, device=src.device)
+    lib().scat_augment_warp_u8(_p(src), _p(plan), _p(dst), B, SH, SW, out_hw[0], out_hw[1], int(bool(hwc)), _stream())
+    return dst
+
+
 def fuse_sum(terms, relu=True):
     """relu?(sum of terms), terms = [(tensor [B,C,H>>k,W>>k], scale|None, shift|None, k)] in the order they are added
     (one pass; include/scat_hip.h scat_fuse_sum)."""
