@@ -1479,23 +1479,36 @@ def _deferred_splitk_reduces(ops, lib):
     assert sum(bool(torch.isnan(o).all()) for o in stale) == npend
 
 
-@pytest.mark.parametrize("B,C,K,H", [(5, 256, 64, 28), (3, 512, 128, 28), (2, 256, 64, 56)])
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("B,C,K,H", [(5, 256, 64, 28), (3, 512, 128, 28), (2, 256, 64, 56),
+                                     (5, 192, 64, 28), (3, 320, 128, 28),      # a partial last 128-row tile
+                                     (96, 256, 64, 56)])                       # the benchmarked size (layer1 -> layer2)
 def test_bn_backward_sums_in_the_data_gradient_epilogue(ops, B, C, K, H):
     """The gradient of a Bottleneck output is completed by the next block's conv1 data gradient, accumulated onto the
     shortcut's gradient (models/resnet.py:93-96).  Armed (scat_epilogue_bnb_arm), that kernel's epilogue applies the
     output's sign mask and leaves bn3's backward sums: the masked gradient must be bit for bit what the accumulate followed
-    by scat_bn_bwd_pre writes, coef3 / d-gamma / d-beta the same to rounding (fp32 tile sums, then fp64)."""
-    c3 = g(t(701, "c3", (B, C, H, H)) * 1.3 + 0.2)
-    res = g(t(702, "res", (B, C, H, H)))
+    by scat_bn_bwd_pre writes, coef3 / d-gamma / d-beta the same to rounding (fp32 tile sums, then fp64).
+
+    And against a reference that is not the library: the masked accumulated gradient, coef3, d-gamma and d-beta from fp64
+    torch on the CPU (tests/test_gpu_guard.py bn3_reference), 2e-5 for the gradient (a contraction) and the 1e-5 this test
+    holds the sums to.  The sign of the block output is taken from the library's mask after that mask has been checked
+    against the fp64 output wherever the fp64 value is not within rounding of zero (there either sign is right, and a
+    reference that chose the other one would differ by a whole gradient element, not by rounding)."""
+    # (the hash-based generator of synth takes seconds per 77 M elements: torch's for the batch-96 case)
+    mk = t if B < 96 else (lambda seed, name, shape: torch.randn(shape, generator=torch.Generator().manual_seed(seed)))
+    c3_c, res_c = mk(701, "c3", (B, C, H, H)) * 1.3 + 0.2, mk(702, "res", (B, C, H, H))
+    dc1_c, w1_c, g_old_c = mk(705, "dc1", (B, K, H, H)), t(706, "w1", (K, C, 1, 1)) * 0.1, mk(707, "gold", (B, C, H, H))
+    c3 = g(c3_c)
+    res = g(res_c)
     gamma = g(torch.from_numpy(synth.uniform(703, "g", (C,), 0.5, 1.5)))
     beta = g(torch.from_numpy(synth.uniform(704, "b", (C,), -0.3, 0.3)))
     rm, rv = g(torch.zeros(C)), g(torch.ones(C))
     mean, invstd, scale, shift = ops.bn_train_stats(c3, gamma, beta, rm, rv)
     out, mask = ops.bn_apply(c3, scale, shift, res, True, want_mask=True)
     assert mask is not None
-    dc1 = g(t(705, "dc1", (B, K, H, H)))
-    w1 = g(t(706, "w1", (K, C, 1, 1)) * 0.1)
-    g_old = g(t(707, "gold", (B, C, H, H)))
+    dc1 = g(dc1_c)
+    w1 = g(w1_c)
+    g_old = g(g_old_c)
     # reference: accumulate, then the reduction pass
     ref = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True)
     coef_r, dg_r, db_r = ops.bn_bwd_pre(ref, c3, True, scale, shift, mean, invstd, gamma, y_mask=mask)
@@ -1512,6 +1525,27 @@ def test_bn_backward_sums_in_the_data_gradient_epilogue(ops, B, C, K, H):
     # the arm is one-shot: the next call is the plain accumulate again
     again = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True)
     assert ops.epilogue_bnb_groups() == 0 and not torch.equal(again, ref)
+    del again, ref, res, g_old, dc1
+    # ---- fp64, independent of the library's own unfused pair
+    from test_gpu_guard import bn3_reference
+
+    v = lambda a: a.cpu().double().view(1, -1, 1, 1)
+    a64, r64 = c3_c.double() * v(scale), res_c.double()
+    y64 = a64 + v(shift) + r64
+    sure = y64.abs() > 4e-7 * (a64.abs() + v(shift).abs() + r64.abs())      # (two fp32 roundings of the fused form)
+    del a64, r64
+    sign = ((mask.view(-1, 1) >> torch.arange(4, device=DEV, dtype=torch.uint8)) & 1).bool().view(B, C, H, H).cpu()
+    assert float(sure.double().mean()) > 0.9999 and torch.equal(sign[sure], (y64 > 0)[sure])
+    del y64, sure
+    g64, coef64, dg64, db64 = bn3_reference(c3_c, sign, gamma.cpu(), mean.cpu(), invstd.cpu(), g_old_c, dc1_c, w1_c)
+    e_g, e_dg, e_db = rel_err(new, g64), rel_err(dg_n, dg64), rel_err(db_n, db64)
+    e_c = [rel_err(coef_n[k], coef64[k]) for k in range(3)]
+    print(f"armed bn3 epilogue ({B},{C},{K},{H}) against fp64: g {e_g:.2e} d-gamma {e_dg:.2e} d-beta {e_db:.2e} coef3 "
+          f"{e_c[0]:.2e} {e_c[1]:.2e} {e_c[2]:.2e}")
+    assert e_g < 2e-5 and e_dg < 1e-5 and e_db < 1e-5 and max(e_c) < 1e-5
+    # the unfused pair against the same reference
+    assert rel_err(dg_r, dg64) < 1e-5 and rel_err(db_r, db64) < 1e-5
+    assert all(rel_err(coef_r[k], coef64[k]) < 1e-5 for k in range(3))
 
 
 # ---------------------------------------------------------------------------------------------------------------
