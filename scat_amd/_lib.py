@@ -1,5 +1,5 @@
-"""ctypes binding of libscat_hip.so. Prototypes are parsed from include/scat_hip.h, so the
-header is the single source of truth for the C ABI. The product path has NO fallback: if the
+"""ctypes binding of libscat_hip.so. Prototypes are parsed from include/scat_hip.h (the train step) and
+include/scat_eval.h (on-device evaluation), so the headers are the single source of truth for the C ABI. The product path has NO fallback: if the
 library is missing, importing a kernel raises."""
 from __future__ import annotations
 
@@ -9,6 +9,8 @@ import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "include", "scat_hip.h")
+EVAL_HEADER = os.path.join(HERE, "..", "include", "scat_eval.h")
+HEADERS = (HEADER, EVAL_HEADER)   # every public header of the one library; parse_header() defaults to the first
 LIBPATH = os.path.join(HERE, "libscat_hip.so")
 if os.environ.get("SCAT_LIBPATH"):
     # measurement tools only (tools/pw_stamp.py, rows_stamp.py): the -DSCAT_DIAG build whose kernels can overwrite their
@@ -66,7 +68,9 @@ class _Lib:
         if torch.cuda.is_available():
             torch.cuda.init()
         self.cdll = ctypes.CDLL(LIBPATH)
-        self.protos = parse_header()
+        self.protos = {}
+        for h in HEADERS:
+            self.protos.update(parse_header(h))
         for name, (rt, at) in self.protos.items():
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = rt

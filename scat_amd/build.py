@@ -23,6 +23,10 @@ def _sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+def _public_headers_mtime():
+    return max(os.path.getmtime(os.path.join(HERE, "..", "include", h)) for h in ("scat_hip.h", "scat_eval.h"))
+
+
 def _deps_mtime():
     m = 0.0
     for root, _, files in os.walk(CSRC):
@@ -31,8 +35,7 @@ def _deps_mtime():
         for f in files:
             if f.endswith((".h", ".hip")):
                 m = max(m, os.path.getmtime(os.path.join(root, f)))
-    m = max(m, os.path.getmtime(os.path.join(HERE, "..", "include", "scat_hip.h")))
-    return m
+    return max(m, _public_headers_mtime())
 
 
 DIAG_OUT = os.path.join(HERE, "..", "tools", "_bin", "libscat_hip_diag.so")
@@ -58,7 +61,7 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
         return OUT
     os.makedirs(OBJ, exist_ok=True)
     hdr_m = max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith(".h"))
-    hdr_m = max(hdr_m, os.path.getmtime(os.path.join(HERE, "..", "include", "scat_hip.h")))
+    hdr_m = max(hdr_m, _public_headers_mtime())
 
     def one(src):
         o = os.path.join(OBJ, src[:-4] + ".o")

@@ -1084,6 +1084,74 @@ def augment_warp_u8(src, plan, out_hw=(224, 224), hwc=True):
     return dst
 
 
+EVAL_RECORD_HEAD = 8   # doubles in front of the counts of a record row (layout: include/scat_eval.h scat_eval_accumulate)
+
+
+def eval_frame_mask(x, blank_sum=150528.0, tol=2000.0):
+    """The blank-frame rule of eval.py:817-823 on a batch x [B,...] fp32 -> keep [B] uint8: 1 where the frame is scored,
+    0 where it is blank padding; sample 0 is always kept, as in the reference (include/scat_eval.h scat_eval_frame_mask)."""
+    if not x.is_cuda:
+        raise ScatError("eval_frame_mask needs a GPU tensor (no CPU fallback on the product path)")
+    if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 2 and x.shape[0] > 0 and x[0].numel() > 0):
+        raise ScatError(f"eval_frame_mask needs a contiguous fp32 batch [B,...], got {x.dtype} {tuple(x.shape)} "
+                        f"contiguous={x.is_contiguous()}")
+    B, n = x.shape[0], x[0].numel()
+    keep = torch.empty((B,), dtype=torch.uint8, device=x.device)
+    ws = workspace(lib().scat_eval_frame_mask_ws(B, n), x.device, "eval")
+    lib().scat_eval_frame_mask(_p(x), _p(keep), B, n, float(blank_sum), float(tol), _p(ws), ws.numel(), _stream())
+    return keep
+
+
+def eval_accumulate(out, labels, thresholds, keep=None, record=None, want_per_sample=False, want_aligned=False):
+    """Scores of one batch (include/scat_eval.h scat_eval_accumulate).  out [B,66] fp32; labels [B,105] or [B,166] fp32 as
+    eval.py:849-855 slices them, or a pair (gt3d [B,63], gt2d [B,42]); thresholds: fp32 GPU tensor [T] (mm) or a sequence;
+    keep: uint8 [B] from eval_frame_mask or None; record: an fp64 GPU row [8 + 2T] to write (a row of a caller's table)
+    or None for a new one.  -> (record, per_sample [B,4] fp64 | None, aligned [B,21,3] fp32 | None)."""
+    pair = isinstance(labels, (tuple, list))
+    ts = (out, *labels) if pair else (out, labels)
+    if not all(t.is_cuda for t in ts):
+        raise ScatError("eval_accumulate needs GPU tensors (no CPU fallback on the product path)")
+    _chk(*ts)
+    B = out.shape[0]
+    if out.dim() != 2 or out.shape[1] != 66 or B == 0:
+        raise ScatError(f"eval_accumulate needs network outputs [B,66], got {tuple(out.shape)}")
+    if pair:
+        gt3d, gt2d = labels
+        if gt3d.reshape(gt3d.shape[0], -1).shape != (B, 63) or gt2d.reshape(gt2d.shape[0], -1).shape != (B, 42):
+            raise ScatError(f"eval_accumulate needs gt3d [{B},63] and gt2d [{B},42], got {tuple(gt3d.shape)} and "
+                            f"{tuple(gt2d.shape)}")
+        # one row stride serves both operands (as in scat_loss_fwd_bwd): 63 walks gt3d; gt2d is re-laid to that stride
+        g2 = torch.zeros((B, 63), dtype=torch.float32, device=out.device)
+        g2[:, :42] = gt2d.reshape(B, 42)
+        p3, p2, ld = gt3d.data_ptr(), g2.data_ptr(), 63
+    else:
+        if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] not in (105, 166):
+            raise ScatError(f"eval_accumulate needs labels [{B},105] or [{B},166] (eval.py:849-855), got "
+                            f"{tuple(labels.shape)}")
+        ld = labels.shape[1]
+        o3, o2 = (0, 63) if ld == 105 else (61, 124)
+        p3, p2 = labels.data_ptr() + 4 * o3, labels.data_ptr() + 4 * o2
+    if not isinstance(thresholds, torch.Tensor):
+        thresholds = torch.as_tensor([float(t) for t in thresholds], dtype=torch.float32).to(out.device)
+    if not (thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.is_contiguous() and thresholds.dim() == 1):
+        raise ScatError("eval_accumulate needs thresholds as a contiguous fp32 GPU vector (no CPU fallback on the product path)")
+    T = thresholds.numel()
+    if keep is not None and not (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous()
+                                 and tuple(keep.shape) == (B,)):
+        raise ScatError(f"eval_accumulate needs keep as a contiguous uint8 GPU vector [{B}]")
+    if record is None:
+        record = torch.empty((EVAL_RECORD_HEAD + 2 * T,), dtype=torch.float64, device=out.device)
+    elif not (record.is_cuda and record.dtype == torch.float64 and record.is_contiguous()
+              and tuple(record.shape) == (EVAL_RECORD_HEAD + 2 * T,)):
+        raise ScatError(f"eval_accumulate needs record as a contiguous fp64 GPU row [{EVAL_RECORD_HEAD + 2 * T}]")
+    per_sample = torch.empty((B, 4), dtype=torch.float64, device=out.device) if want_per_sample else None
+    aligned = torch.empty((B, 21, 3), dtype=torch.float32, device=out.device) if want_aligned else None
+    ws = workspace(lib().scat_eval_accumulate_ws(B, T), out.device, "eval")
+    lib().scat_eval_accumulate(_p(out), p3, p2, ld, _p(keep), _p(thresholds), T, _p(record), _p(per_sample), _p(aligned), B,
+                               _p(ws), ws.numel(), _stream())
+    return record, per_sample, aligned
+
+
 def fuse_sum(terms, relu=True):
     """relu?(sum of terms), terms = [(tensor [B,C,H>>k,W>>k], scale|None, shift|None, k)] in the order they are added
     (one pass; include/scat_hip.h scat_fuse_sum)."""
