@@ -106,7 +106,7 @@ void wgrad_pw_launch(const WgPwPlan& p, const float* dy, const float* x, float* 
                      const float* dy2 = nullptr, const float* coef3 = nullptr);
 // row-walking 3x3 / stride-1 weight gradient for 32- and 64-channel layers (conv_wgrad_rows.hip)
 bool wgrad_rows_ok(int B, int Cin, int H, int W, int Cout, int KH, int stride, int pad, const void* dy, const void* x);
-int64_t wgrad_rows_ws(int B, int Cin, int H, int W, int Cout);
+int wgrad_rows_splits(int B, int Cin, int H, int W, int Cout);   // slabs of Cout x Cin*9 floats it writes (>= 1)
 int wgrad_rows_launch(const float* dy, const float* x, float* slab, int B, int Cin, int H, int W, int Cout,
                       const float* in_scale, const float* in_shift, int in_relu, hipStream_t st);
 __global__ void splitk_reduce_kernel(const float* __restrict__ slab, float* __restrict__ out, int64_t n, int splits,

@@ -1,7 +1,5 @@
 // Convolution weight-gradient: dW[Cout][Cin*KH*KW] = dY[Cout][pixels] * im2col(X)[pixels][Cin*KH*KW],
 // contraction over B*OH*OW pixels, deterministic two-stage split-K (slabs + fixed-order sum).
-#include <vector>
-
 #include "conv_common.h"
 
 namespace scat {
@@ -73,88 +71,8 @@ __global__ __launch_bounds__(64 * WAVES) void splitk_reduce4_kernel(const float4
     out[e] = s;
 }
 
-// ---- deferred reduces: ONE grouped launch for the fixed-order sums of many weight gradients
-// A ResNet-50 backward issues 54 of the launches above, 6-12 us each, every one behind its contraction on the weight-
-// gradient stream.  With scat_splitk_defer(1) in force (per host thread) a reduce is not launched but recorded; the caller
-// keeps every recorded slab intact (its own workspace per contraction) until scat_splitk_reduce_flush() sums them all
-// with one launch: a workgroup finds its job in a table passed in the kernel arguments (<= 48 jobs per launch) and runs
-// the four-wavefront body above — the result depends on (splits, 4) only, bit-reproducible like the single launches.
-struct ReduceJob {
-    const float4* slab;
-    float4* out;
-    int64_t n4;
-    int splits, accumulate, blk0, pad;
-};
-constexpr int RG_MAX = 48;
-struct ReduceTable {
-    ReduceJob j[RG_MAX];
-    int njobs;
-};
-
-__global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceTable t) {
-    __shared__ float4 part[4][64];
-    int lo = 0, hi = t.njobs - 1;
-    const int b = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (t.j[mid].blk0 <= b) lo = mid;
-        else hi = mid - 1;
-    }
-    const float4* __restrict__ slab = t.j[lo].slab;
-    float4* __restrict__ out = t.j[lo].out;
-    const int64_t n4 = t.j[lo].n4;
-    const int splits = t.j[lo].splits, accumulate = t.j[lo].accumulate;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t e = (int64_t)(b - t.j[lo].blk0) * 64 + lane;
-    const bool live = e < n4;
-    const int per = (splits + 3) / 4;
-    const int z0 = wave * per, z1 = min(z0 + per, splits);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) {
-        int z = z0;
-        for (; z + 8 <= z1; z += 8) {
-            float4 v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = slab[(int64_t)(z + q) * n4 + e];
-            s.x += ((v[0].x + v[1].x) + (v[2].x + v[3].x)) + ((v[4].x + v[5].x) + (v[6].x + v[7].x));
-            s.y += ((v[0].y + v[1].y) + (v[2].y + v[3].y)) + ((v[4].y + v[5].y) + (v[6].y + v[7].y));
-            s.z += ((v[0].z + v[1].z) + (v[2].z + v[3].z)) + ((v[4].z + v[5].z) + (v[6].z + v[7].z));
-            s.w += ((v[0].w + v[1].w) + (v[2].w + v[3].w)) + ((v[4].w + v[5].w) + (v[6].w + v[7].w));
-        }
-        for (; z < z1; ++z) {
-            const float4 v = slab[(int64_t)z * n4 + e];
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    }
-    part[wave][lane] = s;
-    __syncthreads();
-    if (wave != 0 || !live) return;
-    s = part[0][lane];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        const float4 v = part[w][lane];
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    if (accumulate) {
-        const float4 o = out[e];
-        s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
-    }
-    out[e] = s;
-}
-
-struct ReduceDefer {
-    bool on = false;
-    std::vector<ReduceJob> jobs;
-};
-static thread_local ReduceDefer g_rdefer;
-
 void launch_splitk_reduce(const float* slab, float* out, int64_t n, int splits, int accumulate, hipStream_t st) {
     static const int vec = diag_env_int("SCAT_REDUCE_VEC", 1);
-    if (g_rdefer.on && n % 4 == 0 && (((uintptr_t)slab | (uintptr_t)out) & 15) == 0 && n / 4 < (1ll << 30)) {
-        g_rdefer.jobs.push_back(ReduceJob{(const float4*)slab, (float4*)out, n / 4, splits, accumulate, 0, 0});
-        append_kernel_label("_rdefer");
-        return;
-    }
     if (vec && n % 4 == 0 && (((uintptr_t)slab | (uintptr_t)out) & 15) == 0) {
         const int64_t n4 = n / 4;
         const dim3 grid((unsigned)((n4 + 63) / 64));
@@ -234,148 +152,19 @@ static bool wgrad_split_ok(int KH, int stride, int pad, int Cout, int Cin) {
     return ((KH == 1 && pad == 0 && stride == 1) || (KH == 3 && pad == 1)) && (int64_t)Cout * Cin * KH * KH > minmn;
 }
 
-}  // namespace scat
-
-using namespace scat;
-
-extern "C" int64_t scat_conv2d_wgrad_ws(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
-    int OH, OW;
-    if (check_geom("scat_conv2d_wgrad_ws", B, Cin, H, W, Cout, KH, KW, stride, pad, &OH, &OW)) return -1;
-    WgradPlan p = wgrad_plan(B, Cin, Cout, KH * KW, OH, OW);
-    int64_t need = p.splits > 1 ? (int64_t)p.splits * p.M * p.N * sizeof(float) : 0;
-    if (wgrad_split_ok(KH, stride, pad, Cout, Cin)) {            // the math mode may change between this query and the call
-        WgSplitPlan q = wgrad_split_plan(B, Cin, Cout, KH * KW, OH * OW);
-        int64_t n2 = q.splits > 1 ? (int64_t)q.splits * q.M * q.N * sizeof(float) : 0;
-        if (n2 > need) need = n2;
-    }
-    if (wgrad_rows_ok(B, Cin, H, W, Cout, KH, stride, pad, nullptr, nullptr)) {
-        const int64_t n3 = wgrad_rows_ws(B, Cin, H, W, Cout);
-        if (n3 > need) need = n3;
-    }
-    if (KH == 1 && stride == 1 && pad == 0) {
-        const WgPwPlan w = wgrad_pw_plan(B, Cin, Cout, OH * OW, false, nullptr, nullptr);
-        const int64_t n4 = w.ok && w.splits > 1 ? (int64_t)w.splits * Cout * Cin * sizeof(float) : 0;
-        if (n4 > need) need = n4;
-    }
-    return need;
-}
-
-// Weight gradient of a 1x1/stride-1 convolution from a BatchNorm backward that was never materialised:
-// dy = ca*g + cb*z + cc per output channel (see scat_bn_bwd_pre / scat_conv1x1_s1_bnb).  Split products only.
-extern "C" int scat_conv1x1_wgrad_bnb(const float* g, const float* z, const float* coef3, const float* x, float* dw,
-                                      int B, int Cin, int HW, int Cout, const float* in_scale, const float* in_shift,
-                                      int in_relu, void* ws, int64_t ws_bytes, void* stream) {
-    SCAT_REQUIRE(g && z && coef3 && x && dw, SCAT_E_ARG, "scat_conv1x1_wgrad_bnb: null pointer");
-    SCAT_REQUIRE(math_mode() == 1, SCAT_E_ARG, "scat_conv1x1_wgrad_bnb: needs the split-operand product mode");
-    SCAT_REQUIRE(B > 0 && Cin > 0 && HW > 0 && Cout > 0, SCAT_E_SHAPE, "scat_conv1x1_wgrad_bnb: non-positive dimension");
-    SCAT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), SCAT_E_ARG, "scat_conv1x1_wgrad_bnb: scale/shift pair");
-    SCAT_REQUIRE(fits_i32((int64_t)B * Cout * HW * 4) && fits_i32((int64_t)B * Cin * HW * 4), SCAT_E_SHAPE,
-                 "scat_conv1x1_wgrad_bnb: tensor exceeds 32-bit byte offsets");
-    hipStream_t st = (hipStream_t)stream;
-    const WgPwPlan w = wgrad_pw_plan(B, Cin, Cout, HW, true, g, x);
-    if (w.ok && ((uintptr_t)z & 15) == 0) {
-        const int64_t needw = w.splits > 1 ? (int64_t)w.splits * Cout * Cin * sizeof(float) : 0;
-        SCAT_REQUIRE(ws_bytes >= needw && (needw == 0 || ws), SCAT_E_WORKSPACE,
-                     "scat_conv1x1_wgrad_bnb: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)needw);
-        wgrad_pw_launch(w, g, x, w.splits > 1 ? (float*)ws : dw, B, Cin, HW, Cout, in_scale, in_shift,
-                        in_scale ? in_relu : 0, st, z, coef3);
-        SCAT_LAUNCH_CHECK("scat_conv1x1_wgrad_bnb(pw)");
-        if (w.splits > 1) {
-            launch_splitk_reduce((const float*)ws, dw, (int64_t)Cout * Cin, w.splits, 0, st);
-            SCAT_LAUNCH_CHECK("scat_conv1x1_wgrad_bnb(reduce)");
-        }
-        return SCAT_OK;
-    }
-    const WgSplitPlan q = wgrad_split_plan(B, Cin, Cout, 1, HW);
-    const int64_t need = q.splits > 1 ? (int64_t)q.splits * q.M * q.N * sizeof(float) : 0;
-    SCAT_REQUIRE(ws_bytes >= need && (need == 0 || ws), SCAT_E_WORKSPACE,
-                 "scat_conv1x1_wgrad_bnb: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
-    wgrad_split_launch(q, g, x, q.splits > 1 ? (float*)ws : dw, B, Cin, 1, HW, Cout, 1, 1, in_scale, in_shift,
-                       in_scale ? in_relu : 0, st, z, coef3);
-    SCAT_LAUNCH_CHECK("scat_conv1x1_wgrad_bnb");
-    if (q.splits > 1) {
-        int64_t n = (int64_t)q.M * q.N;
-        launch_splitk_reduce((const float*)ws, dw, n, q.splits, 0, st);
-        SCAT_LAUNCH_CHECK("scat_conv1x1_wgrad_bnb(reduce)");
-    }
-    return SCAT_OK;
-}
-extern "C" int64_t scat_conv1x1_wgrad_bnb_ws(int B, int Cin, int HW, int Cout) {
-    const WgSplitPlan q = wgrad_split_plan(B, Cin, Cout, 1, HW);
-    int64_t need = q.splits > 1 ? (int64_t)q.splits * q.M * q.N * sizeof(float) : 0;
-    const WgPwPlan w = wgrad_pw_plan(B, Cin, Cout, HW, true, nullptr, nullptr);
-    const int64_t needw = w.ok && w.splits > 1 ? (int64_t)w.splits * Cout * Cin * sizeof(float) : 0;
-    return needw > need ? needw : need;
-}
-
-extern "C" int scat_conv2d_wgrad(const float* dy, const float* x, float* dw, int B, int Cin, int H, int W, int Cout,
-                                 int KH, int KW, int stride, int pad, const float* in_scale, const float* in_shift,
-                                 int in_relu, void* ws, int64_t ws_bytes, void* stream) {
-    int OH, OW;
-    if (int e = check_geom("scat_conv2d_wgrad", B, Cin, H, W, Cout, KH, KW, stride, pad, &OH, &OW)) return e;
-    SCAT_REQUIRE(dy && x && dw, SCAT_E_ARG, "scat_conv2d_wgrad: null pointer");
-    SCAT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), SCAT_E_ARG, "scat_conv2d_wgrad: scale/shift pair");
-    SCAT_REQUIRE(!(in_scale && KH == 7), SCAT_E_SHAPE, "scat_conv2d_wgrad: fused input transform not built for 7x7");
-    if (!in_scale) in_relu = 0;
-    if (math_mode() == 1 && KH == KW && wgrad_rows_ok(B, Cin, H, W, Cout, KH, stride, pad, dy, x) &&
-        fits_i32((int64_t)B * Cout * H * W * 4) && fits_i32((int64_t)B * Cin * H * W * 4)) {
-        const int64_t need3 = wgrad_rows_ws(B, Cin, H, W, Cout);
-        SCAT_REQUIRE(ws && ws_bytes >= need3, SCAT_E_WORKSPACE, "scat_conv2d_wgrad: workspace %lld < %lld bytes",
-                     (long long)ws_bytes, (long long)need3);
-        hipStream_t st3 = (hipStream_t)stream;
-        const int splits = wgrad_rows_launch(dy, x, (float*)ws, B, Cin, H, W, Cout, in_scale, in_shift, in_relu, st3);
-        SCAT_LAUNCH_CHECK("scat_conv2d_wgrad(rows)");
-        launch_splitk_reduce((const float*)ws, dw, (int64_t)Cout * Cin * 9, splits, 0, st3);
-        SCAT_LAUNCH_CHECK("scat_conv2d_wgrad(reduce)");
-        return SCAT_OK;
-    }
-    if (math_mode() == 1 && KH == 1 && KW == 1 && stride == 1 && pad == 0 &&
-        fits_i32((int64_t)B * Cout * H * W * 4) && fits_i32((int64_t)B * Cin * H * W * 4)) {
-        const WgPwPlan w = wgrad_pw_plan(B, Cin, Cout, H * W, false, dy, x);
-        if (w.ok) {
-            const int64_t need4 = w.splits > 1 ? (int64_t)w.splits * Cout * Cin * sizeof(float) : 0;
-            SCAT_REQUIRE(ws_bytes >= need4 && (need4 == 0 || ws), SCAT_E_WORKSPACE,
-                         "scat_conv2d_wgrad: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need4);
-            hipStream_t st4 = (hipStream_t)stream;
-            wgrad_pw_launch(w, dy, x, w.splits > 1 ? (float*)ws : dw, B, Cin, H * W, Cout, in_scale, in_shift, in_relu, st4);
-            SCAT_LAUNCH_CHECK("scat_conv2d_wgrad(pw)");
-            if (w.splits > 1) {
-                launch_splitk_reduce((const float*)ws, dw, (int64_t)Cout * Cin, w.splits, 0, st4);
-                SCAT_LAUNCH_CHECK("scat_conv2d_wgrad(reduce)");
-            }
-            return SCAT_OK;
-        }
-    }
-    if (math_mode() == 1 && wgrad_split_ok(KH, stride, pad, Cout, Cin)) {
-        const WgSplitPlan q = wgrad_split_plan(B, Cin, Cout, KH * KW, OH * OW);
-        const int64_t need2 = q.splits > 1 ? (int64_t)q.splits * q.M * q.N * sizeof(float) : 0;
-        SCAT_REQUIRE(ws_bytes >= need2 && (need2 == 0 || ws), SCAT_E_WORKSPACE,
-                     "scat_conv2d_wgrad: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need2);
-        hipStream_t st2 = (hipStream_t)stream;
-        wgrad_split_launch(q, dy, x, q.splits > 1 ? (float*)ws : dw, B, Cin, H, W, Cout, KH * KW, stride, in_scale,
-                           in_shift, in_relu, st2);
-        SCAT_LAUNCH_CHECK("scat_conv2d_wgrad");
-        if (q.splits > 1) {
-            int64_t n = (int64_t)q.M * q.N;
-            launch_splitk_reduce((const float*)ws, dw, n, q.splits, 0, st2);
-            SCAT_LAUNCH_CHECK("scat_conv2d_wgrad(reduce)");
-        }
-        return SCAT_OK;
-    }
-    WgradPlan p = wgrad_plan(B, Cin, Cout, KH * KW, OH, OW);
-    int64_t need = p.splits > 1 ? (int64_t)p.splits * p.M * p.N * sizeof(float) : 0;
-    SCAT_REQUIRE(ws_bytes >= need && (need == 0 || ws), SCAT_E_WORKSPACE,
-                 "scat_conv2d_wgrad: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)need);
+// fp32 gather engine: any geometry check_geom admits, either product mode, any alignment
+static void wgrad_f32_launch(const WgradPlan& p, const float* dy, const float* x, float* out, int B, int Cin, int H, int W,
+                             int Cout, int KH, int stride, int pad, int OH, int OW, const float* in_scale,
+                             const float* in_shift, int in_relu, hipStream_t st) {
     const int npix = B * OH * OW;
     // A: dy as [Cout][pixel]; B: x through the forward conv arithmetic as [pixel][(ci,kh,kw)]
     GatherDesc da{dy, nullptr, nullptr, 0, Cout, OH, OW, OH, OW, 1, 0, 0, 0, npix, Cout, FastDiv::make(OH * OW),
                   FastDiv::make(OW), (int64_t)B * Cout * OH * OW};
-    GatherDesc db{x, in_scale, in_shift, in_relu, Cin, H, W, OH, OW, stride, 1, -pad, -pad, npix, Cin * KH * KW,
+    GatherDesc db{x, in_scale, in_shift, in_relu, Cin, H, W, OH, OW, stride, 1, -pad, -pad, npix, Cin * KH * KH,
                   FastDiv::make(OH * OW), FastDiv::make(OW), (int64_t)B * Cin * H * W};
     OutDesc dc{};
-    dc.p = p.splits > 1 ? (float*)ws : dw;
+    dc.p = out;
     dc.mode = 0; dc.si = p.N; dc.sj = 1; dc.sz = (int64_t)p.M * p.N; dc.I = p.M; dc.J = p.N; dc.n = (int64_t)p.M * p.N;
-    hipStream_t st = (hipStream_t)stream;
     const bool av4 = (OH * OW) % 4 == 0 && ((uintptr_t)dy & 15) == 0;
     const bool bv4 = KH <= 3 && stride == 1 && OH == H && OW == W && (H * W) % 4 == 0 && W >= 4 &&
                      ((uintptr_t)x & 15) == 0;
@@ -391,41 +180,156 @@ extern "C" int scat_conv2d_wgrad(const float* dy, const float* x, float* dw, int
         if (av4) wgrad_gemm<7, 7, true, false>(p, da, db, dc, st);
         else wgrad_gemm<7, 7, false, false>(p, da, db, dc, st);
     }
-    SCAT_LAUNCH_CHECK("scat_conv2d_wgrad");
-    if (p.splits > 1) {
-        int64_t n = (int64_t)p.M * p.N;
-        launch_splitk_reduce((const float*)ws, dw, n, p.splits, 0, st);
-        SCAT_LAUNCH_CHECK("scat_conv2d_wgrad(reduce)");
+}
+
+// ---- one plan for the workspace query and the launch
+// wgrad_candidates() is the only place that names the engines of a weight gradient: it yields those the geometry
+// admits, in priority order, each with its plan and the run-time conditions under which a launch may take it.  The _ws
+// queries return the largest slab need over the candidates, the entry points launch the first candidate whose conditions
+// hold — so a query cannot promise less than its launch writes, whatever the math mode and the pointers turn out to be.
+enum WgEngine { WG_ROWS, WG_PW, WG_SPLIT, WG_F32 };
+
+struct WgGeom {
+    int B, Cin, H, W, Cout, KH, stride, pad, OH, OW;
+    bool bnb;   // folded BatchNorm backward (scat_conv1x1_wgrad_bnb): 1x1 / stride 1 over H = 1, W = pixels per image
+};
+
+struct WgCand {
+    WgEngine eng;
+    int splits;       // slabs of Cout x Cin*KH*KH floats the engine writes ...
+    bool slabs;       // ... into the workspace, reduced into dw afterwards; false: one split, straight into dw
+    bool split_math;  // takes the call only in product mode 1,
+    bool aligned;     // only with dy, x (and z) on 16-byte boundaries,
+    bool i32;         // only while both tensors stay within 32-bit byte offsets
+    WgPwPlan pw;      // the plan of eng (the rows engine plans inside its launch)
+    WgSplitPlan sp;
+    WgradPlan f32;
+};
+
+static int64_t wg_slab_bytes(const WgGeom& g, const WgCand& c) {
+    return c.slabs ? (int64_t)c.splits * g.Cout * g.Cin * g.KH * g.KH * sizeof(float) : 0;
+}
+
+static int wgrad_candidates(const WgGeom& g, WgCand c[4]) {
+    int n = 0;
+    if (!g.bnb && wgrad_rows_ok(g.B, g.Cin, g.H, g.W, g.Cout, g.KH, g.stride, g.pad, nullptr, nullptr)) {
+        c[n] = WgCand{WG_ROWS, wgrad_rows_splits(g.B, g.Cin, g.H, g.W, g.Cout), true, true, true, true};   // always slabs
+        ++n;
     }
-    return SCAT_OK;
-}
-
-
-/* Deferred split-K reduces (include/scat_hip.h). */
-extern "C" int scat_splitk_defer(int on) {
-    scat::g_rdefer.on = on != 0;
-    return SCAT_OK;
-}
-extern "C" int scat_splitk_reduce_pending(void) { return (int)scat::g_rdefer.jobs.size(); }
-extern "C" int scat_splitk_reduce_discard(void) {
-    scat::g_rdefer.jobs.clear();
-    return SCAT_OK;
-}
-extern "C" int scat_splitk_reduce_flush(void* stream) {
-    auto& jobs = scat::g_rdefer.jobs;
-    hipStream_t st = (hipStream_t)stream;
-    for (size_t i = 0; i < jobs.size(); i += scat::RG_MAX) {
-        scat::ReduceTable t{};
-        int blk = 0;
-        t.njobs = (int)(jobs.size() - i < (size_t)scat::RG_MAX ? jobs.size() - i : (size_t)scat::RG_MAX);
-        for (int k = 0; k < t.njobs; ++k) {
-            t.j[k] = jobs[i + k];
-            t.j[k].blk0 = blk;
-            blk += (int)((t.j[k].n4 + 63) / 64);
+    if (g.KH == 1 && g.stride == 1 && g.pad == 0) {
+        const WgPwPlan w = wgrad_pw_plan(g.B, g.Cin, g.Cout, g.H * g.W, g.bnb, nullptr, nullptr);
+        if (w.ok) {
+            c[n] = WgCand{WG_PW, w.splits, w.splits > 1, true, true, true};
+            c[n++].pw = w;
         }
-        hipLaunchKernelGGL(scat::splitk_reduce_group_kernel, dim3(blk), dim3(256), 0, st, t);
     }
-    jobs.clear();
-    SCAT_LAUNCH_CHECK("scat_splitk_reduce_flush");
+    if (g.bnb || wgrad_split_ok(g.KH, g.stride, g.pad, g.Cout, g.Cin)) {
+        const WgSplitPlan q = wgrad_split_plan(g.B, g.Cin, g.Cout, g.KH * g.KH, g.OH * g.OW);
+        c[n] = WgCand{WG_SPLIT, q.splits, q.splits > 1, true, false, false};
+        c[n++].sp = q;
+    }
+    if (!g.bnb) {       // (the folded form has split products only: its entry point insists on product mode 1)
+        const WgradPlan p = wgrad_plan(g.B, g.Cin, g.Cout, g.KH * g.KH, g.OH, g.OW);
+        c[n] = WgCand{WG_F32, p.splits, p.splits > 1, false, false, false};
+        c[n++].f32 = p;
+    }
+    return n;
+}
+
+static int64_t wgrad_ws_bytes(const WgGeom& g) {
+    WgCand c[4];
+    const int n = wgrad_candidates(g, c);
+    int64_t need = 0;
+    for (int i = 0; i < n; ++i)
+        if (wg_slab_bytes(g, c[i]) > need) need = wg_slab_bytes(g, c[i]);
+    return need;
+}
+
+// dy2 / coef3: the folded BatchNorm backward's second tensor and coefficients (g.bnb), else null
+static int wgrad_run(const char* who, const WgGeom& g, const float* dy, const float* dy2, const float* coef3,
+                     const float* x, float* dw, const float* in_scale, const float* in_shift, int in_relu, void* ws,
+                     int64_t ws_bytes, hipStream_t st) {
+    WgCand c[4];
+    const int n = wgrad_candidates(g, c);
+    const bool split_math = math_mode() == 1;
+    const bool aligned = (((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)x) & 15) == 0;
+    const bool i32 = fits_i32((int64_t)g.B * g.Cout * g.H * g.W * 4) && fits_i32((int64_t)g.B * g.Cin * g.H * g.W * 4);
+    const WgCand* e = nullptr;
+    for (int i = 0; i < n && !e; ++i)
+        if ((split_math || !c[i].split_math) && (aligned || !c[i].aligned) && (i32 || !c[i].i32)) e = &c[i];
+    SCAT_REQUIRE(e, SCAT_E_ARG, "%s: no engine takes this call", who);
+    const int64_t need = wg_slab_bytes(g, *e);
+    SCAT_REQUIRE(ws_bytes >= need && (need == 0 || ws), SCAT_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who,
+                 (long long)ws_bytes, (long long)need);
+    float* out = e->slabs ? (float*)ws : dw;
+    if (!in_scale) in_relu = 0;
+    const char* tag = "";
+    switch (e->eng) {
+    case WG_ROWS:
+        tag = "(rows)";
+        wgrad_rows_launch(dy, x, out, g.B, g.Cin, g.H, g.W, g.Cout, in_scale, in_shift, in_relu, st);
+        break;
+    case WG_PW:
+        tag = "(pw)";
+        wgrad_pw_launch(e->pw, dy, x, out, g.B, g.Cin, g.H * g.W, g.Cout, in_scale, in_shift, in_relu, st, dy2, coef3);
+        break;
+    case WG_SPLIT:
+        wgrad_split_launch(e->sp, dy, x, out, g.B, g.Cin, g.H, g.W, g.Cout, g.KH * g.KH, g.stride, in_scale, in_shift,
+                           in_relu, st, dy2, coef3);
+        break;
+    case WG_F32:
+        wgrad_f32_launch(e->f32, dy, x, out, g.B, g.Cin, g.H, g.W, g.Cout, g.KH, g.stride, g.pad, g.OH, g.OW, in_scale,
+                         in_shift, in_relu, st);
+        break;
+    }
+    char name[64];      // (composed only when a check fails)
+    SCAT_LAUNCH_CHECK((snprintf(name, sizeof name, "%s%s", who, tag), name));
+    if (e->slabs) {
+        launch_splitk_reduce((const float*)ws, dw, (int64_t)g.Cout * g.Cin * g.KH * g.KH, e->splits, 0, st);
+        SCAT_LAUNCH_CHECK((snprintf(name, sizeof name, "%s(reduce)", who), name));
+    }
     return SCAT_OK;
+}
+
+static WgGeom wg_geom_bnb(int B, int Cin, int HW, int Cout) { return WgGeom{B, Cin, 1, HW, Cout, 1, 1, 0, 1, HW, true}; }
+
+}  // namespace scat
+
+using namespace scat;
+
+extern "C" int64_t scat_conv2d_wgrad_ws(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad) {
+    int OH, OW;
+    if (check_geom("scat_conv2d_wgrad_ws", B, Cin, H, W, Cout, KH, KW, stride, pad, &OH, &OW)) return -1;
+    return wgrad_ws_bytes(WgGeom{B, Cin, H, W, Cout, KH, stride, pad, OH, OW, false});
+}
+
+extern "C" int scat_conv2d_wgrad(const float* dy, const float* x, float* dw, int B, int Cin, int H, int W, int Cout,
+                                 int KH, int KW, int stride, int pad, const float* in_scale, const float* in_shift,
+                                 int in_relu, void* ws, int64_t ws_bytes, void* stream) {
+    int OH, OW;
+    if (int e = check_geom("scat_conv2d_wgrad", B, Cin, H, W, Cout, KH, KW, stride, pad, &OH, &OW)) return e;
+    SCAT_REQUIRE(dy && x && dw, SCAT_E_ARG, "scat_conv2d_wgrad: null pointer");
+    SCAT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), SCAT_E_ARG, "scat_conv2d_wgrad: scale/shift pair");
+    SCAT_REQUIRE(!(in_scale && KH == 7), SCAT_E_SHAPE, "scat_conv2d_wgrad: fused input transform not built for 7x7");
+    return wgrad_run("scat_conv2d_wgrad", WgGeom{B, Cin, H, W, Cout, KH, stride, pad, OH, OW, false}, dy, nullptr, nullptr,
+                     x, dw, in_scale, in_shift, in_relu, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// Weight gradient of a 1x1/stride-1 convolution from a BatchNorm backward that was never materialised:
+// dy = ca*g + cb*z + cc per output channel (see scat_bn_bwd_pre / scat_conv1x1_s1_bnb).  Split products only.
+extern "C" int64_t scat_conv1x1_wgrad_bnb_ws(int B, int Cin, int HW, int Cout) {
+    return wgrad_ws_bytes(wg_geom_bnb(B, Cin, HW, Cout));
+}
+
+extern "C" int scat_conv1x1_wgrad_bnb(const float* g, const float* z, const float* coef3, const float* x, float* dw,
+                                      int B, int Cin, int HW, int Cout, const float* in_scale, const float* in_shift,
+                                      int in_relu, void* ws, int64_t ws_bytes, void* stream) {
+    SCAT_REQUIRE(g && z && coef3 && x && dw, SCAT_E_ARG, "scat_conv1x1_wgrad_bnb: null pointer");
+    SCAT_REQUIRE(math_mode() == 1, SCAT_E_ARG, "scat_conv1x1_wgrad_bnb: needs the split-operand product mode");
+    SCAT_REQUIRE(B > 0 && Cin > 0 && HW > 0 && Cout > 0, SCAT_E_SHAPE, "scat_conv1x1_wgrad_bnb: non-positive dimension");
+    SCAT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), SCAT_E_ARG, "scat_conv1x1_wgrad_bnb: scale/shift pair");
+    SCAT_REQUIRE(fits_i32((int64_t)B * Cout * HW * 4) && fits_i32((int64_t)B * Cin * HW * 4), SCAT_E_SHAPE,
+                 "scat_conv1x1_wgrad_bnb: tensor exceeds 32-bit byte offsets");
+    return wgrad_run("scat_conv1x1_wgrad_bnb", wg_geom_bnb(B, Cin, HW, Cout), g, z, coef3, x, dw, in_scale, in_shift,
+                     in_relu, ws, ws_bytes, (hipStream_t)stream);
 }

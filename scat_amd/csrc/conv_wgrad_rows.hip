@@ -501,10 +501,10 @@ static void rows_plan(int B, int Cin, int H, int W, int Cout, int& rpw, int& spl
     splits = (rows + rpw - 1) / rpw;
 }
 
-int64_t wgrad_rows_ws(int B, int Cin, int H, int W, int Cout) {
+int wgrad_rows_splits(int B, int Cin, int H, int W, int Cout) {
     int rpw, splits;
     rows_plan(B, Cin, H, W, Cout, rpw, splits);
-    return (int64_t)splits * Cout * Cin * 9 * sizeof(float);
+    return splits;
 }
 
 // slab -> dw by launch_splitk_reduce (caller); returns the number of slabs

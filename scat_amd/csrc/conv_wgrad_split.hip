@@ -489,8 +489,9 @@ static void launch_wg(const WgDesc& d, const OutDesc& dc, int splits, hipStream_
 
 template <int KK, bool TF, bool S2>
 static void launch_wg_tile(int mi, int ni, const WgDesc& d, const OutDesc& dc, int splits, hipStream_t st) {
-    if (mi == 2 && ni == 2) launch_wg<KK, 2, 2, TF, S2>(d, dc, splits, st);
-    else if (mi == 2) launch_wg<KK, 2, 1, TF, S2>(d, dc, splits, st);
+    if (mi == 2 && ni == 2) {       // shipped build: wg_pc_mode() is 1 and the producer / consumer kernel took these
+        if constexpr (kDiag) launch_wg<KK, 2, 2, TF, S2>(d, dc, splits, st);
+    } else if (mi == 2) launch_wg<KK, 2, 1, TF, S2>(d, dc, splits, st);
     else if (ni == 2) launch_wg<KK, 1, 2, TF, S2>(d, dc, splits, st);
     else launch_wg<KK, 1, 1, TF, S2>(d, dc, splits, st);
 }
@@ -526,8 +527,9 @@ WgSplitPlan wgrad_split_plan(int B, int Cin, int Cout, int KK, int HW) {
 
 template <bool TF>
 static void launch_wg_dsa(int mi, int ni, const WgDesc& d, const OutDesc& dc, int splits, hipStream_t st) {
-    if (mi == 2 && ni == 2) launch_wg<1, 2, 2, TF, false, true>(d, dc, splits, st);
-    else if (mi == 2) launch_wg<1, 2, 1, TF, false, true>(d, dc, splits, st);
+    if (mi == 2 && ni == 2) {
+        if constexpr (kDiag) launch_wg<1, 2, 2, TF, false, true>(d, dc, splits, st);
+    } else if (mi == 2) launch_wg<1, 2, 1, TF, false, true>(d, dc, splits, st);
     else if (ni == 2) launch_wg<1, 1, 2, TF, false, true>(d, dc, splits, st);
     else launch_wg<1, 1, 1, TF, false, true>(d, dc, splits, st);
 }
@@ -549,39 +551,37 @@ void wgrad_split_launch(const WgSplitPlan& p, const float* dy, const float* x, f
     dc.n = (int64_t)p.M * p.N;
     set_kernel_label("wgrad%s%s_split_%dx%dx16%s%s_split%d", KK == 9 ? "3x3" : "1x1", stride == 2 ? "_s2" : "", 64 * p.mi,
                      64 * p.ni, in_scale ? "_tf" : "", dy2 ? "_bnb" : "", p.splits);
+    // 1x1 / stride 2 never comes here (wgrad_split_ok leaves it to the fp32 engine): those forms are not instantiated
+    const bool tf = in_scale != nullptr;
     if (wg_pc_mode() && p.mi == 2 && p.ni == 2) {
-        const bool tf = in_scale != nullptr;
         set_kernel_label("wgrad%s%s_split_pc128x128x16%s%s_split%d", KK == 9 ? "3x3" : "1x1", stride == 2 ? "_s2" : "",
                          in_scale ? "_tf" : "", dy2 ? "_bnb" : "", p.splits);
         if (dy2) {
             if (tf) launch_wg_pc<1, true, false, true>(d, dc, p.splits, st);
             else launch_wg_pc<1, false, false, true>(d, dc, p.splits, st);
         } else if (stride == 2) {
-            if (KK == 9) { if (tf) launch_wg_pc<9, true, true, false>(d, dc, p.splits, st); else launch_wg_pc<9, false, true, false>(d, dc, p.splits, st); }
-            else { if (tf) launch_wg_pc<1, true, true, false>(d, dc, p.splits, st); else launch_wg_pc<1, false, true, false>(d, dc, p.splits, st); }
+            if (tf) launch_wg_pc<9, true, true, false>(d, dc, p.splits, st);
+            else launch_wg_pc<9, false, true, false>(d, dc, p.splits, st);
         } else if (KK == 9) {
-            if (tf) launch_wg_pc<9, true, false, false>(d, dc, p.splits, st); else launch_wg_pc<9, false, false, false>(d, dc, p.splits, st);
+            if (tf) launch_wg_pc<9, true, false, false>(d, dc, p.splits, st);
+            else launch_wg_pc<9, false, false, false>(d, dc, p.splits, st);
         } else {
-            if (tf) launch_wg_pc<1, true, false, false>(d, dc, p.splits, st); else launch_wg_pc<1, false, false, false>(d, dc, p.splits, st);
+            if (tf) launch_wg_pc<1, true, false, false>(d, dc, p.splits, st);
+            else launch_wg_pc<1, false, false, false>(d, dc, p.splits, st);
         }
         return;
     }
     if (dy2) {      // 1x1 / stride 1 only (checked by the caller)
-        if (in_scale) launch_wg_dsa<true>(p.mi, p.ni, d, dc, p.splits, st);
+        if (tf) launch_wg_dsa<true>(p.mi, p.ni, d, dc, p.splits, st);
         else launch_wg_dsa<false>(p.mi, p.ni, d, dc, p.splits, st);
     } else if (stride == 2) {
-        if (KK == 9) {
-            if (in_scale) launch_wg_tile<9, true, true>(p.mi, p.ni, d, dc, p.splits, st);
-            else launch_wg_tile<9, false, true>(p.mi, p.ni, d, dc, p.splits, st);
-        } else {
-            if (in_scale) launch_wg_tile<1, true, true>(p.mi, p.ni, d, dc, p.splits, st);
-            else launch_wg_tile<1, false, true>(p.mi, p.ni, d, dc, p.splits, st);
-        }
+        if (tf) launch_wg_tile<9, true, true>(p.mi, p.ni, d, dc, p.splits, st);
+        else launch_wg_tile<9, false, true>(p.mi, p.ni, d, dc, p.splits, st);
     } else if (KK == 9) {
-        if (in_scale) launch_wg_tile<9, true, false>(p.mi, p.ni, d, dc, p.splits, st);
+        if (tf) launch_wg_tile<9, true, false>(p.mi, p.ni, d, dc, p.splits, st);
         else launch_wg_tile<9, false, false>(p.mi, p.ni, d, dc, p.splits, st);
     } else {
-        if (in_scale) launch_wg_tile<1, true, false>(p.mi, p.ni, d, dc, p.splits, st);
+        if (tf) launch_wg_tile<1, true, false>(p.mi, p.ni, d, dc, p.splits, st);
         else launch_wg_tile<1, false, false>(p.mi, p.ni, d, dc, p.splits, st);
     }
 }

@@ -33,9 +33,7 @@ def test_header_declares_the_path():
                                                 # host-side state of the NEXT launch of this thread, no device work
                                                 "scat_epilogue_stats_arm", "scat_epilogue_stats_arm_shift", "scat_epilogue_stats_groups",
                                                 "scat_epilogue_bnb_arm", "scat_epilogue_bnb_groups",
-                                                "scat_streamk_arm",
-                                                # host-side record of reduces to be flushed later (the flush takes the stream)
-                                                "scat_splitk_defer", "scat_splitk_reduce_pending", "scat_splitk_reduce_discard"):
+                                                "scat_streamk_arm"):
             assert args[-1][1] == "stream", name
     # every prototype cites the reference file it replaces somewhere in the header
     src = open(os.path.join(ROOT, "include", "scat_hip.h")).read()
@@ -65,6 +63,27 @@ def test_errors_surface_without_a_gpu(built):
         L.scat_attention_fwd(1, 1, 1, 2, 21, 8, 32, 0.1, 0)
     assert L.scat_conv2d_wgrad_ws(96, 64, 56, 56, 64, 3, 3, 1, 1) > 0
     assert L.scat_gemm_ws(2016, 1536, 784) >= 0
+
+
+def test_wgrad_workspace_queries_are_pinned(built):
+    """scat_conv2d_wgrad_ws / scat_conv1x1_wgrad_bnb_ws return, byte for byte, what tests/golden/wgrad_ws.json recorded
+    before the query and the launch were given one plan (key: "<query>:<its arguments>"): every geometry of CONVS and
+    HRNET_B96 at batch 96 and 8 and the shapes of the weight-gradient tests.  The queries launch nothing."""
+    import json
+
+    from scat_amd._lib import lib
+    from test_gpu_ops import CONVS, HRNET_B96
+
+    L = lib()
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "wgrad_ws.json")))
+    for B in (96, 8):
+        for cin, cout, k, s, p, H in CONVS + [(cin, cout, k, s, k // 2, H) for cin, cout, k, s, H in HRNET_B96]:
+            assert f"conv2d_wgrad_ws:{B},{cin},{H},{H},{cout},{k},{k},{s},{p}" in gold
+            if k == 1 and s == 1:
+                assert f"conv1x1_wgrad_bnb_ws:{B},{cin},{H * H},{cout}" in gold
+    for key, want in gold.items():
+        fn, args = key.split(":")
+        assert getattr(L, "scat_" + fn)(*map(int, args.split(","))) == want, key
 
 
 def test_product_has_no_cpu_fallback():

@@ -324,6 +324,69 @@ def _c13(t):
               .view(cout, cin, 1, 1))
 
 
+# The weight-gradient entry points with a workspace of exactly the bytes their _ws query promises, inside the arena: the
+# query and the launch take their engine from one plan (csrc/conv_wgrad.hip wgrad_candidates), and a launch that wrote one
+# slab more than the query returned would land in the guard behind "ws".  One shape per engine, the smallest the tests of
+# tests/test_gpu_ops.py choose it at; a skewed dy or x drops the rows and pointwise engines to the next candidate under
+# the same query; product mode 0 takes the fp32 engine everywhere.  -> compute in every placement
+_WG_EXACT = [
+    # B, cin, cout, H, W, k, stride, label in product mode 1 when aligned
+    (5, 32, 64, 7, 40, 3, 1, "wgrad3x3_rows_32x288x16"), (2, 128, 128, 9, 28, 3, 1, "wgrad3x3_rows_64x576x16"),
+    (3, 320, 192, 5, 5, 1, 1, "wgrad1x1_pw_"), (2, 128, 128, 14, 18, 1, 1, "wgrad1x1_pw_"),
+    (2, 20, 136, 9, 13, 3, 1, "wgrad3x3_split_"), (2, 20, 136, 9, 13, 3, 2, "wgrad3x3_s2_split_"),
+    (2, 144, 136, 8, 14, 1, 2, "wgrad1x1_128x64x32"),
+]
+
+
+def _exact_ws(t, nbytes):
+    """(pointer, bytes) of a guarded workspace of exactly nbytes (its contents are the kernel's business)"""
+    if nbytes == 0:
+        return 0, 0
+    return P(t.arena.place(nbytes, 0, torch.uint8, name="ws", out=True, finite=False)), nbytes
+
+
+@case("wgrad_exact_workspace", ("scat_conv2d_wgrad",), 2e-5, direct=True, maths=(0, 1))
+def _c13b(t):
+    for B, cin, cout, H, W, k, s, label in _WG_EXACT:
+        key, p, w_shape = f"{cin}_{cout}_{H}x{W}k{k}s{s}", k // 2, (cout, cin, k, k)
+        OH, OW = t.ops.conv_out_hw(H, W, k, s, p)
+        x = t.once("x" + key, lambda: R(230 + H, (B, cin, H, W)))
+        dy = t.once("dy" + key, lambda: R(231 + H, (B, cout, OH, OW)))
+        sc = t.once("sc" + key, lambda: U(232, (cin,), 0.5, 1.5))
+        sh = t.once("sh" + key, lambda: U(233, (cin,), 0.1, 0.6))
+        dyg, xg, scg, shg = t.inp(dy, "dy" + key), t.inp(x, "x" + key), t.inp(sc, "scale"), t.inp(sh, "shift")
+        need = t.lib.scat_conv2d_wgrad_ws(B, cin, H, W, cout, k, k, s, p)
+        assert need >= 0
+        for tf in (False, True):
+            dw = t.buf(w_shape, "dw" + key)
+            ws, nb = _exact_ws(t, need)
+            t.lib.scat_conv2d_wgrad(P(dyg), P(xg), P(dw), B, cin, H, W, cout, k, k, s, p, P(scg) if tf else 0,
+                                    P(shg) if tf else 0, int(tf), ws, nb, t.stream())
+            if t.aligned:
+                want = label if t.math == 1 else f"wgrad{k}x{k}_{64 if cout <= 64 else 128}x64x32"
+                assert t.label().startswith(want), (t.label(), want)
+            a = (lambda: F.relu(x.double() * v4(sc.double()) + v4(sh.double()))) if tf else (lambda: x.double())
+            t.out(f"dw{key}tf{int(tf)}", dw,
+                  lambda: torch.nn.grad.conv2d_weight(a(), w_shape, dy.double(), stride=s, padding=p))
+
+
+@case("wgrad_bnb_exact_workspace", ("scat_conv1x1_wgrad_bnb",), 2e-5, direct=True, maths=(1,))
+def _c13c(t):
+    B, cin, cout, H, W = 2, 128, 128, 14, 18
+    g = t.once("g", lambda: R(240, (B, cout, H, W)))
+    z = t.once("z", lambda: R(241, (B, cout, H, W)))
+    coef = t.once("coef", lambda: U(242, (3, cout), -0.5, 0.5))
+    x = t.once("x", lambda: R(243, (B, cin, H, W)))
+    gg, zg, cg, xg = t.inp(g, "g"), t.inp(z, "z"), t.inp(coef, "coef3"), t.inp(x, "x")
+    dw = t.buf((cout, cin, 1, 1), "dw")
+    ws, nb = _exact_ws(t, t.lib.scat_conv1x1_wgrad_bnb_ws(B, cin, H * W, cout))
+    t.lib.scat_conv1x1_wgrad_bnb(P(gg), P(zg), P(cg), P(xg), P(dw), B, cin, H * W, cout, 0, 0, 0, ws, nb, t.stream())
+    if t.aligned:
+        assert t.label().startswith("wgrad1x1_pw_") and "_bnb" in t.label(), t.label()
+    dz = lambda: v4(coef[0].double()) * g.double() + v4(coef[1].double()) * z.double() + v4(coef[2].double())
+    t.out("dw", dw, lambda: torch.einsum("nop,nip->oi", dz().flatten(2), x.double().flatten(2)).view(cout, cin, 1, 1))
+
+
 # the general engine itself (channel counts no specialised kernel takes), bias on a ragged channel count, and the
 # transposed-weights data gradient
 @case("conv_generic", ("scat_conv2d_fwd", "scat_conv2d_dgrad", "scat_conv2d_wt", "scat_conv2d_wgrad"), 2e-5,
