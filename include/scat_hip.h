@@ -6,6 +6,10 @@
  * never synchronises, never allocates, retains no pointer.  Returns 0 or a negative
  * SCAT_E_* code; scat_last_error() gives the thread-local message.  fp32 everywhere.
  *
+ * Workspaces: an entry point that takes (ws, ws_bytes) names the scat_*_ws query that sizes it and the alignment ws
+ * needs.  ws_bytes is checked against that query on the host before anything is launched, and the launch writes no byte
+ * past it; a missing, short or misaligned workspace is SCAT_E_WORKSPACE unless the entry point says otherwise.
+ *
  * Each entry point names the reference call it stands in for (paths relative to the
  * reference checkout tomguluson92/SCAT).  The reference has no FFI of its own (it is pure
  * torch.nn); the binding a maintainer adds is the ctypes stub in INTEGRATION.md.
@@ -44,7 +48,7 @@ int scat_conv2d_dgrad(const float* dy, const float* wt, float* dx, int B, int Ci
                       int KW, int stride, int pad, int accumulate, void* stream);
 /* Stride-2 data-gradient decomposed by input-pixel parity (1x1/pad 0 and 3x3/pad 1): four stride-1
  * contractions over only the taps that can contribute (1+2+2+4 of 9), i.e. no MFMA work on structural
- * zeros.  Takes the ORIGINAL weights w[Cout,Cin,KH,KW]; ws: scat_conv2d_dgrad_s2_ws() bytes. */
+ * zeros.  Takes the ORIGINAL weights w[Cout,Cin,KH,KW]; ws: scat_conv2d_dgrad_s2_ws() bytes, 16-B aligned. */
 int64_t scat_conv2d_dgrad_s2_ws(int Cin, int Cout, int KH, int KW);
 int scat_conv2d_dgrad_s2(const float* dy, const float* w, float* dx, int B, int Cin, int H, int W, int Cout, int KH,
                          int KW, int pad, int accumulate, void* ws, int64_t ws_bytes, int w_ready, void* stream);
@@ -58,15 +62,15 @@ int scat_set_math_mode(int mode);
 /* 3x3 / stride 1 / pad 1 with an LDS-resident halo (every input element is fetched once per tile instead of
  * once per tap): transposed = 0 -> dst[B,Cout,H,W] = conv(relu(src*scale+shift), w), src[B,Cin,H,W];
  * transposed = 1 -> dst[B,Cin,H,W] (+)= data gradient from src = dy[B,Cout,H,W].  w is the forward weight
- * [Cout,Cin,3,3]; ws: scat_conv3x3_s1_ws() bytes (re-laid weights).  Needs W <= 63.
+ * [Cout,Cin,3,3]; ws: scat_conv3x3_s1_ws() bytes, 16-B aligned (re-laid weights).  Needs W <= 63.
  * Replaces nn.Conv2d(3, padding=1) at models/resnet.py:68-69 and its autograd. */
 int64_t scat_conv3x3_s1_ws(int Cout, int Cin);
 int scat_conv3x3_s1(const float* src, const float* w, float* dst, int B, int Cin, int H, int W, int Cout,
                     int transposed, const float* in_scale, const float* in_shift, int in_relu, int accumulate,
                     void* ws, int64_t ws_bytes, int w_ready, void* stream);
 /* Forward conv (1x1 / 3x3, stride 1 or 2) on the split-operand taps kernel: contraction ordered (tap, channel),
- * weights re-laid and split per call into ws (scat_conv2d_fwd_split_ws bytes).  Needs scat_get_math_mode() == 1 and
- * Cin % 16 == 0.  The library's path for the stride-2 convolutions (models/resnet.py:68,131-135). */
+ * weights re-laid and split per call into ws (scat_conv2d_fwd_split_ws bytes, 16-B aligned).  Needs
+ * scat_get_math_mode() == 1 and Cin % 16 == 0.  The library's path for the stride-2 convolutions (models/resnet.py:68,131-135). */
 int64_t scat_conv2d_fwd_split_ws(int Cout, int Cin, int KH, int KW);
 int scat_conv2d_fwd_split(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int H, int W,
                           int Cout, int KH, int KW, int stride, int pad, const float* in_scale, const float* in_shift,
@@ -74,19 +78,21 @@ int scat_conv2d_fwd_split(const float* x, const float* w, const float* bias, flo
 /* One transformer layer's qkv projection + softmax attention in one launch (models/vision_transformer.py:61-76):
  * qkv[B*n,3*heads*64] = h[B*n,dim] . wqkv^T; attn[B,heads,n,n] = softmax(scale q k^T); ao[B*n,heads*64] = attn . v
  * ('b n (h d)').  One workgroup per (block of 128/n images, head): the block's projection stays in LDS for its
- * attention.  n <= 32, dim % 4 == 0, head dim 64, scat_get_math_mode() == 1.  ws: scat_vit_qkv_attn_fwd_ws bytes. */
+ * attention.  n <= 32, dim % 4 == 0, head dim 64, scat_get_math_mode() == 1.  ws: scat_vit_qkv_attn_fwd_ws bytes,
+ * 16-B aligned (as h must be). */
 int64_t scat_vit_qkv_attn_fwd_ws(int dim, int heads);
 int scat_vit_qkv_attn_fwd(const float* h, const float* wqkv, float* qkv, float* attn, float* ao, int B, int n, int dim,
                           int heads, float scale, void* ws, int64_t ws_bytes, void* stream);
 /* The ResNet stem, Conv2d(3, Cout, 7, stride 2, padding 3, bias=False) (models/resnet.py:105), on split-operand
  * products: contraction over (kh, c, kw) with kw padded to 8, so a k-octet is 8 consecutive input pixels.
- * y[B,Cout,OH,OW]; ws: scat_conv7x7_s2_fwd_split_ws(Cout) bytes.  Needs scat_get_math_mode() == 1. */
+ * y[B,Cout,OH,OW]; ws: scat_conv7x7_s2_fwd_split_ws(Cout) bytes, 16-B aligned.  Needs scat_get_math_mode() == 1. */
 int64_t scat_conv7x7_s2_fwd_split_ws(int Cout);
 int scat_conv7x7_s2_fwd_split(const float* x, const float* w, float* y, int B, int H, int W, int Cout, void* ws,
                               int64_t ws_bytes, void* stream);
 /* Weight gradient of that stem convolution: dw[64,3,7,7] from dy[B,64,OH,OW] and x[B,3,H,W]; one workgroup walks whole
  * output rows with the 7 x 3 input rows they touch in LDS, both MFMA operands split in registers, deterministic split
- * over output rows + fixed-order reduce.  Cout = 64, OW % 16 == 0, OW <= 112.  ws: ..._ws(B, H, W) bytes. */
+ * over output rows + fixed-order reduce.  Cout = 64, OW % 16 == 0, OW <= 112.  ws: ..._ws(B, H, W) bytes, 16-B aligned
+ * (as dy must be). */
 int64_t scat_conv7x7_s2_wgrad_split_ws(int B, int H, int W);
 int scat_conv7x7_s2_wgrad_split(const float* dy, const float* x, float* dw, int B, int H, int W, int Cout, void* ws,
                                 int64_t ws_bytes, void* stream);
@@ -94,8 +100,8 @@ int scat_conv7x7_s2_wgrad_split(const float* dy, const float* x, float* dw, int 
  * Weights go straight from L2 to the MFMA operand registers, activations through LDS 32 channels per barrier.
  * transposed = 0 (forward): w = [M,C] = the conv weight [Cout,Cin];  transposed = 1 (data gradient): w = [C,M] is
  * still the forward weight (M = Cin, C = Cout) and src = dy.  ws: scat_conv1x1_s1_ws(M, C) bytes for the re-laid
- * weights.  Needs C % 16 == 0 and 16-B aligned w/src/ws.  Replaces nn.Conv2d(k=1) at models/resnet.py:65-72 and
- * its autograd. */
+ * weights.  Needs C % 16 == 0 and 16-B aligned w/src/ws (a misaligned ws is SCAT_E_ARG here, with w and src).  Replaces
+ * nn.Conv2d(k=1) at models/resnet.py:65-72 and its autograd. */
 int64_t scat_conv1x1_s1_ws(int M, int C);
 int scat_conv1x1_s1(const float* src, const float* w, float* dst, int B, int C, int HW, int M, int transposed,
                     const float* bias, const float* in_scale, const float* in_shift, int in_relu, int accumulate,
@@ -109,7 +115,7 @@ int scat_conv1x1_s1(const float* src, const float* w, float* dst, int B, int C, 
  * scat_conv1x1_planes: scat_conv1x1_s1 with the activations given as planes (no input transform: it is already in
  * them); the activation path is LDS-DMA only (buffer_load ... lds), bit-identical results.  C % 32 == 0.
  * lds_stages: depth of the LDS ring the activations land in (2: 48 KB, three workgroups per CU; 3: 72 KB, two, one
- * more stage in flight); 0 = the library's choice.
+ * more stage in flight); 0 = the library's choice.  ws: scat_conv1x1_s1_ws(M, C) bytes, 16-B aligned.
  * Replaces nn.Conv2d(k=1) forward / input gradient at models/resnet.py:65-72,84-92. */
 int64_t scat_planes_bytes(int B, int C, int HW);
 int scat_planes_from_f32(const float* src, void* planes, int B, int C, int HW, const float* in_scale,
@@ -140,8 +146,8 @@ int scat_streamk_error(const void* buf, int64_t bytes, void* stream);
  * memory at jobs_out (scat_wprep_job_bytes() each), numbered from block blk0, and returns the first free block (< 0:
  * SCAT_E_*); the caller concatenates the jobs of a whole network, uploads the table once and runs it with ONE
  * launch after each weight update (scat_wprep_run).  ws must be the buffer later passed to the entry point
- * (16-B aligned, the entry's *_ws() bytes); Cout/Cin/KH/KW/pad are those of w[Cout,Cin,KH,KW].  The library
- * keeps no state: the table and the workspaces belong to the caller. */
+ * (16-B aligned, the entry's *_ws() bytes; a null, misaligned or short one is SCAT_E_WORKSPACE); Cout/Cin/KH/KW/pad
+ * are those of w[Cout,Cin,KH,KW].  The library keeps no state: the table and the workspaces belong to the caller. */
 #define SCAT_WPREP_CONV1X1_FWD 0   /* scat_conv1x1_s1, transposed = 0 */
 #define SCAT_WPREP_CONV1X1_DGRAD 1 /* scat_conv1x1_s1, transposed = 1; scat_conv1x1_s1_bnb */
 #define SCAT_WPREP_CONV3X3_FWD 2   /* scat_conv3x3_s1, transposed = 0 */
@@ -155,7 +161,8 @@ int scat_wprep_run(const void* jobs_dev, int njobs, int64_t nblocks, void* strea
 /* wt[Cin][Cout*KH*KW] = w[Cout][Cin][KH][KW] re-laid for the data-gradient contraction. */
 int scat_conv2d_wt(const float* w, float* wt, int Cout, int Cin, int KH, int KW, void* stream);
 /* dw[Cout,Cin,KH,KW] = sum over pixels dy * relu(x*scale+shift).  Deterministic two-stage
- * split-K (no float atomics).  ws: scat_conv2d_wgrad_ws() bytes. */
+ * split-K (no float atomics).  ws: scat_conv2d_wgrad_ws() bytes, 4-B aligned (the reduce takes 16-byte loads when ws
+ * allows them); unused, and may be null, where the query is 0. */
 int64_t scat_conv2d_wgrad_ws(int B, int Cin, int H, int W, int Cout, int KH, int KW, int stride, int pad);
 int scat_conv2d_wgrad(const float* dy, const float* x, float* dw, int B, int Cin, int H, int W, int Cout, int KH,
                       int KW, int stride, int pad, const float* in_scale, const float* in_shift, int in_relu,
@@ -165,7 +172,8 @@ int scat_conv2d_wgrad(const float* dy, const float* x, float* dw, int B, int Cin
  *      models/resnet.py:116; hand_net.py:353 ----
  * C[M,N] (+)= op(A)[M,K] * op(B)[K,N] (+ bias).  A(i,k) = a[i*a_si + k*a_sk], B(k,j) = b[k*b_sk + j*b_sj],
  * C(i,j) = c[i*c_si + j*c_sj]; one of each stride pair must be 1.  bias_mode 0 none, 1 bias[i], 2 bias[j].
- * ws may be NULL (no split-K). */
+ * ws: scat_gemm_ws() bytes, 4-B aligned, for the split-K slabs.  It may be NULL, short or misaligned: the call then runs
+ * as a single pass over K (label ..._split1), bias and accumulate applied by the contraction kernel itself. */
 int64_t scat_gemm_ws(int M, int N, int K);
 int scat_gemm(const float* a, int64_t a_si, int64_t a_sk, const float* b, int64_t b_sk, int64_t b_sj, float* c,
               int64_t c_si, int64_t c_sj, int M, int N, int K, const float* bias, int bias_mode, int accumulate,
@@ -190,7 +198,7 @@ int scat_gemm_group(const ScatGemmProblem* problems, int n, void* ws, int64_t ws
 /* The same contraction on split-operand products (scat_get_math_mode() == 1), for the dense projections of the ViT
  * blocks (models/vision_transformer.py:52,57,76: to_qkv, to_out and their gradients; FeedForward :33-35):
  * c[M,N] (+)= op(a)[M,K] . b[K,N] (+ bias_n[N]); b and c row-major; a is [M,K] row-major, or stored [K,M] when
- * a_transposed.  ws: scat_gemm_split_ws(M, K) bytes.  scat_transpose2d: dst[C,R] = src[R,C] (the W^T a forward
+ * a_transposed.  ws: scat_gemm_split_ws(M, K) bytes, 16-B aligned.  scat_transpose2d: dst[C,R] = src[R,C] (the W^T a forward
  * projection needs as its b operand). */
 int64_t scat_gemm_split_ws(int M, int K);
 int scat_gemm_split(const float* a, int a_transposed, const float* b, float* c, int M, int N, int K, const float* bias_n,
@@ -200,7 +208,8 @@ int scat_transpose2d(const float* src, float* dst, int R, int C, void* stream);
 /* ---- BatchNorm2d, training + inference: models/resnet.py:68-73,108,131 (eps 1e-5, momentum .1) ----
  * stats: per-channel batch mean / biased variance (fp64 accumulation, fixed reduction order), folded
  * into scale = gamma*invstd, shift = beta - mean*scale; running stats updated (unbiased var).
- * ws: scat_bn_ws(C) bytes. save_mean / save_invstd [C] are kept for backward. */
+ * ws: scat_bn_ws(B, C, HW) bytes, 8-B aligned (doubles and 64-bit agent-scope atomics live in it) — the same for
+ * scat_bn_bwd, scat_bn_bwd_maxpool and scat_bn_bwd_pre.  save_mean / save_invstd [C] are kept for backward. */
 int64_t scat_bn_ws(int B, int C, int HW);
 int scat_bn_train_stats(const float* x, int B, int C, int HW, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
@@ -236,7 +245,7 @@ int scat_bn_apply(const float* x, const float* scale, const float* shift, const 
                   const float* res_shift, int relu, float* y, uint8_t* mask_out, int B, int C, int HW, void* stream);
 /* backward of y = [relu](bn(x) [+res]):  g = dy * (mask);  mask from y_out>0 (if y_out), from the sign mask of
  * scat_bn_apply (if y_mask), else from x*scale+shift>0 (if relu), else 1.  Produces dgamma, dbeta, dx and (if dres)
- * dres (+)= g. */
+ * dres (+)= g.  ws: scat_bn_ws(B, C, HW) bytes, 8-B aligned. */
 int scat_bn_bwd(const float* dy, const float* x, const float* y_out, const uint8_t* y_mask, int relu, const float* scale,
                 const float* shift, const float* save_mean, const float* save_invstd, const float* gamma,
                 float* dgamma, float* dbeta, float* dx, float* dres, int dres_accumulate, int B, int C, int HW,
@@ -244,7 +253,8 @@ int scat_bn_bwd(const float* dy, const float* x, const float* y_out, const uint8
 
 /* the same backward for the stem (models/resnet.py:108-112 conv1 -> bn1 -> relu -> maxpool): dy is the gradient of the
  * 3x3 / stride-2 / pad-1 max-pool's OUTPUT [B,C,H/2,W/2] with its arg-max taps idx (scat_maxpool3x3s2_fwd); the scattered
- * full-resolution gradient is never written.  dx[B,C,H,W].  Even H, W % 4 == 0.  ws: scat_bn_ws(B, C, H*W). */
+ * full-resolution gradient is never written.  dx[B,C,H,W].  Even H, W % 4 == 0.  ws: scat_bn_ws(B, C, H*W) bytes,
+ * 8-B aligned. */
 int scat_bn_bwd_maxpool(const float* dy_pooled, const int8_t* idx, const float* x, int relu, const float* scale,
                         const float* shift, const float* save_mean, const float* save_invstd, const float* gamma,
                         float* dgamma, float* dbeta, float* dx, int B, int C, int H, int W, void* ws, int64_t ws_bytes,
@@ -253,7 +263,8 @@ int scat_bn_bwd_maxpool(const float* dy_pooled, const int8_t* idx, const float* 
  * (g = dy * mask; g is also the residual branch's gradient), reduces the per-channel sums and emits
  * coef3[3*C] = (ca | cb | cc) with  dx = ca*g + cb*x + cc;  the consumers of dx apply that while loading their
  * operand (scat_conv1x1_s1_bnb, scat_conv1x1_wgrad_bnb).  dy_add (nullable): a second contribution to the incoming
- * gradient, summed while loading (dy_g <- mask * (dy_g + dy_add)).  Needs HW % 4 == 0 and 16-B aligned tensors. */
+ * gradient, summed while loading (dy_g <- mask * (dy_g + dy_add)).  Needs HW % 4 == 0 and 16-B aligned tensors.
+ * ws: scat_bn_ws(B, C, HW) bytes, 8-B aligned. */
 int scat_bn_bwd_pre(float* dy_g, const float* dy_add, const float* x, const float* y_out, const uint8_t* y_mask, int relu, const float* scale,
                     const float* shift, const float* save_mean, const float* save_invstd, const float* gamma,
                     float* dgamma, float* dbeta, float* coef3, int B, int C, int HW, void* ws, int64_t ws_bytes,
@@ -273,10 +284,12 @@ int scat_bn_bwd_pre_partials(const float* partials, int groups, int B, int C, in
                              const float* save_invstd, const float* gamma, float* dgamma, float* dbeta, float* coef3,
                              void* stream);
 /* dx[B,Cin,HW] (+)= w^T . (ca*g + cb*z + cc): data gradient of a 1x1 conv whose output gradient is the BatchNorm
- * backward above (g, coef3 from scat_bn_bwd_pre; z = the conv's raw output).  ws: scat_conv1x1_s1_ws(Cin, Cout). */
+ * backward above (g, coef3 from scat_bn_bwd_pre; z = the conv's raw output).  ws: scat_conv1x1_s1_ws(Cin, Cout) bytes,
+ * 16-B aligned. */
 int scat_conv1x1_s1_bnb(const float* g, const float* z, const float* coef3, const float* w, float* dx, int B, int Cin,
                         int HW, int Cout, int accumulate, void* ws, int64_t ws_bytes, int w_ready, void* stream);
-/* dw[Cout,Cin] = sum over pixels (ca*g + cb*z + cc)[co] * relu(x*scale+shift)[ci]: the same conv's weight gradient. */
+/* dw[Cout,Cin] = sum over pixels (ca*g + cb*z + cc)[co] * relu(x*scale+shift)[ci]: the same conv's weight gradient.
+ * ws: scat_conv1x1_wgrad_bnb_ws() bytes, 4-B aligned; unused, and may be null, where the query is 0. */
 int64_t scat_conv1x1_wgrad_bnb_ws(int B, int Cin, int HW, int Cout);
 int scat_conv1x1_wgrad_bnb(const float* g, const float* z, const float* coef3, const float* x, float* dw, int B, int Cin,
                            int HW, int Cout, const float* in_scale, const float* in_shift, int in_relu, void* ws,
@@ -300,8 +313,8 @@ int scat_subsample2(const float* x, float* y, int B, int C, int H, int W, void* 
 int scat_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
                        int rows, int dim, float eps, void* stream);
 int64_t scat_layernorm_bwd_ws(int rows, int dim);
-/* dgamma == dbeta == NULL: the input gradient only (no parameter sums, ws unused) — the pose-length term's replay,
- * models/hand_net.py:396 */
+/* ws: scat_layernorm_bwd_ws(rows, dim) bytes, 4-B aligned.  dgamma == dbeta == NULL: the input gradient only (no
+ * parameter sums, ws unused and may be null) — the pose-length term's replay, models/hand_net.py:396 */
 int scat_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                        float* dx, float* dgamma, float* dbeta, int rows, int dim, void* ws, int64_t ws_bytes,
                        void* stream);
@@ -315,7 +328,8 @@ int scat_attention_bwd(const float* dout, const float* qkv, const float* attn, f
 
 /* ---- performer (FAVOR+) linear attention core: models/vision_performer.py:34-53 ----
  * kqv[B,T,heads,3e] (k|q|v per head, one shared Linear, :17,47), w[m,e] frozen random features (:32);
- * y[B,T,heads*e].  Saved for backward: kp,qp[B,heads,T,m], kptv[B,heads,e,m], ksum[B,heads,m], D[B,heads,T]. */
+ * y[B,T,heads*e].  Saved for backward: kp,qp[B,heads,T,m], kptv[B,heads,e,m], ksum[B,heads,m], D[B,heads,T].
+ * ws of the backward: scat_performer_bwd_ws() bytes, 4-B aligned. */
 int scat_performer_fwd(const float* kqv, const float* w, float* y, float* kp, float* qp, float* kptv, float* ksum,
                        float* D, int B, int T, int heads, int e, int m, void* stream);
 int64_t scat_performer_bwd_ws(int B, int T, int heads, int e, int m);
@@ -338,7 +352,8 @@ int scat_axpy(const float* a, const float* b, float alpha, float* y, int64_t n, 
 int scat_colsum(const float* x, float* out, int rows, int cols, int accumulate, void* stream);
 /* the same with a caller-owned scratch of scat_colsum_ws(rows, cols) bytes (0 for small inputs): tall matrices are summed in
  * row slices by ~1024 workgroups instead of cols / 16, slices added in index order (bias gradients of the token mixers:
- * models/vit.py:40-47 at HRNet's 24 672 x 196 tokens) */
+ * models/vit.py:40-47 at HRNet's 24 672 x 196 tokens).  ws: 4-B aligned; unused, and may be null, where the query is 0
+ * (the call is then scat_colsum). */
 int64_t scat_colsum_ws(int rows, int cols);
 int scat_colsum_sliced(const float* x, float* out, int rows, int cols, int accumulate, void* ws, int64_t ws_bytes, void* stream);
 /* n <= 16 independent column sums as ONE launch, each summed in scat_colsum's order (bit-identical to n calls): the bias
@@ -395,7 +410,7 @@ int scat_token_mean_bwd(const float* dy, float* dx, int B, int T, int D, void* s
  * pred0[b] = mean[P]; pred0[:,3:] += feat_out[b,P-3] (if feat_out); iter x: pred += [feat,pred]·W^T + bias;
  * root_relative: joints -= joint1.  preds[(iters+1),B,P] keeps every iterate for backward; out[B,P].
  * The same loop is the HRNet wrapper's head (hand_net.py:206-211: F=196, P=61, no offsets, not root-relative)
- * and ViP's (vision_performer.py:112-115). */
+ * and ViP's (vision_performer.py:112-115).  ws of the backward: scat_regressor_bwd_ws() bytes, 4-B aligned. */
 int scat_regressor_fwd(const float* feat, const float* feat_out, const float* mean, const float* w, const float* bias,
                        float* preds, float* out, int B, int F, int P, int iters, int root_relative, void* stream);
 int scat_regressor_bwd(const float* dout, const float* feat, const float* preds, const float* w, float* dfeat,

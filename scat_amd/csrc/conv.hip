@@ -227,6 +227,7 @@ extern "C" int scat_conv2d_dgrad_s2(const float* dy, const float* w, float* dx, 
     SCAT_REQUIRE((Cout * KH * KW) % 4 == 0 && Cout % 4 == 0, SCAT_E_SHAPE, "scat_conv2d_dgrad_s2: Cout % 4 != 0");
     SCAT_REQUIRE(ws && ws_bytes >= scat_conv2d_dgrad_s2_ws(Cin, Cout, KH, KW), SCAT_E_WORKSPACE,
                  "scat_conv2d_dgrad_s2: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "scat_conv2d_dgrad_s2: workspace not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (!accumulate && KH == 1) {   // 1x1: only even pixels receive gradient, the rest of dx is zero
         if (hipMemsetAsync(dx, 0, (size_t)B * Cin * H * W * sizeof(float), st) != hipSuccess) {
@@ -235,7 +236,7 @@ extern "C" int scat_conv2d_dgrad_s2(const float* dy, const float* w, float* dx, 
         }
     }
     float* wtc = (float*)ws;
-    const bool split_ok = math_mode() == 1 && Cout % 16 == 0 && ((uintptr_t)ws & 15) == 0;
+    const bool split_ok = math_mode() == 1 && Cout % 16 == 0;
     SCAT_REQUIRE(!w_ready || split_ok, SCAT_E_ARG, "scat_conv2d_dgrad_s2: prepared weights exist for split products only");
     S2Class cls[4];
     const int ncls = dgrad_s2_classes(Cin, Cout, KH, KW, pad, cls);
@@ -297,9 +298,13 @@ extern "C" int64_t scat_wprep_job_bytes(void) { return (int64_t)sizeof(WPrepJob)
 
 extern "C" int64_t scat_wprep_jobs(int kind, const float* w, void* ws, int64_t ws_bytes, int Cout, int Cin, int KH,
                                    int KW, int pad, int64_t blk0, void* jobs_out, int max_jobs, int* njobs_out) {
-    if (!w || !ws || !jobs_out || !njobs_out || Cout <= 0 || Cin <= 0 || max_jobs < 4 || ((uintptr_t)ws & 15)) {
+    if (!w || !jobs_out || !njobs_out || Cout <= 0 || Cin <= 0 || max_jobs < 4) {
         set_error("scat_wprep_jobs: bad argument");
         return SCAT_E_ARG;
+    }
+    if (!ws || ((uintptr_t)ws & 15)) {
+        set_error("scat_wprep_jobs: workspace missing or not 16-byte aligned");
+        return SCAT_E_WORKSPACE;
     }
     WPrepJob jobs[4];
     int n = 1;
@@ -315,11 +320,11 @@ extern "C" int64_t scat_wprep_jobs(int kind, const float* w, void* ws, int64_t w
             break;
         case SCAT_WPREP_CONV3X3_FWD:
             jobs[0] = wprep_job(w, ws, Cout, Cin, 0, 3, 3, 9, 3, 0, 0, 1);
-            need = taps_split_ws(Cout, Cin, 9);
+            need = scat_conv3x3_s1_ws(Cout, Cin);      // (what the entry point itself asks of this buffer)
             break;
         case SCAT_WPREP_CONV3X3_DGRAD:
             jobs[0] = wprep_job(w, ws, Cin, Cout, 1, 3, 3, 9, 3, 0, 0, 1);
-            need = taps_split_ws(Cin, Cout, 9);
+            need = scat_conv3x3_s1_ws(Cout, Cin);      // (what the entry point itself asks of this buffer)
             break;
         case SCAT_WPREP_FWD_SPLIT:
             jobs[0] = wprep_job(w, ws, Cout, Cin, 0, KH, KW, KH * KW, KW, 0, 0, 1);
@@ -327,7 +332,7 @@ extern "C" int64_t scat_wprep_jobs(int kind, const float* w, void* ws, int64_t w
             break;
         case SCAT_WPREP_DGRAD_S2:
             n = dgrad_s2_wprep_jobs(w, ws, Cin, Cout, KH, KW, pad, jobs);
-            need = taps_split_ws(Cin, Cout, KH * KW);
+            need = scat_conv2d_dgrad_s2_ws(Cin, Cout, KH, KW);
             break;
         default:
             set_error("scat_wprep_jobs: unknown kind %d", kind);

@@ -476,6 +476,7 @@ extern "C" int scat_conv3x3_s1(const float* src, const float* w, float* dst, int
     const int Csrc = transposed ? Cout : Cin, Cdst = transposed ? Cin : Cout;
     SCAT_REQUIRE(W + 1 <= 64, SCAT_E_SHAPE, "scat_conv3x3_s1: width > 63 (halo row would not fit one thread per column)");
     SCAT_REQUIRE(ws && ws_bytes >= scat_conv3x3_s1_ws(Cout, Cin), SCAT_E_WORKSPACE, "scat_conv3x3_s1: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "scat_conv3x3_s1: workspace not 16-byte aligned");
     SCAT_REQUIRE(fits_i32((int64_t)B * Csrc * H * W * 4) && fits_i32((int64_t)B * Cdst * H * W * 4) &&
                      fits_i32((int64_t)Cout * Cin * 9 * 4),
                  SCAT_E_SHAPE, "scat_conv3x3_s1: tensor exceeds 32-bit byte offsets");

@@ -261,6 +261,7 @@ static int wgrad_run(const char* who, const WgGeom& g, const float* dy, const fl
     const int64_t need = wg_slab_bytes(g, *e);
     SCAT_REQUIRE(ws_bytes >= need && (need == 0 || ws), SCAT_E_WORKSPACE, "%s: workspace %lld < %lld bytes", who,
                  (long long)ws_bytes, (long long)need);
+    SCAT_REQUIRE(need == 0 || ((uintptr_t)ws & 3) == 0, SCAT_E_WORKSPACE, "%s: workspace not 4-byte aligned", who);
     float* out = e->slabs ? (float*)ws : dw;
     if (!in_scale) in_relu = 0;
     const char* tag = "";

@@ -223,7 +223,8 @@ extern "C" int scat_gemm(const float* a, int64_t a_si, int64_t a_sk, const float
     SCAT_REQUIRE(bias_mode >= 0 && bias_mode <= 2 && (bias_mode == 0 || bias), SCAT_E_ARG, "scat_gemm: bias");
     GemmPlan p = gemm_plan(M, N, K);
     int64_t need = p.splits > 1 ? (int64_t)p.splits * M * N * sizeof(float) : 0;
-    if (need > ws_bytes || (need && !ws)) { p.splits = 1; need = 0; }   // no workspace: single pass
+    // no workspace, a short one, or one that cannot hold floats: single pass
+    if (need > ws_bytes || (need && (!ws || ((uintptr_t)ws & 3)))) { p.splits = 1; need = 0; }
     SCAT_REQUIRE(fits_i32(((int64_t)(M - 1) * a_si + (int64_t)(K - 1) * a_sk + 1) * 4) &&
                      fits_i32(((int64_t)(N - 1) * b_sj + (int64_t)(K - 1) * b_sk + 1) * 4),
                  SCAT_E_SHAPE, "scat_gemm: operand exceeds 2 GiB");

@@ -742,6 +742,7 @@ extern "C" int scat_regressor_bwd(const float* dout, const float* feat, const fl
     SCAT_REQUIRE(B > 0 && F > 0 && P >= 9 && P <= 128 && iters >= 0, SCAT_E_SHAPE, "scat_regressor_bwd: need 9 <= P <= 128");
     SCAT_REQUIRE(ws && ws_bytes >= scat_regressor_bwd_ws(B, F, P, iters), SCAT_E_WORKSPACE,
                  "scat_regressor_bwd: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 3) == 0, SCAT_E_WORKSPACE, "scat_regressor_bwd: workspace not 4-byte aligned");
     float* deltas = (float*)ws;
     float* dsum = deltas + (int64_t)(iters > 0 ? iters : 1) * B * P;
     hipStream_t st = (hipStream_t)stream;

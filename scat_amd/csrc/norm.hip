@@ -971,6 +971,7 @@ extern "C" int scat_bn_train_stats(const float* x, int B, int C, int HW, const f
     SCAT_REQUIRE(B > 0 && C > 0 && HW > 0, SCAT_E_SHAPE, "scat_bn_train_stats: non-positive dimension");
     SCAT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), SCAT_E_ARG, "scat_bn_train_stats: running pair");
     SCAT_REQUIRE(ws && ws_bytes >= scat_bn_ws(B, C, HW), SCAT_E_WORKSPACE, "scat_bn_train_stats: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 7) == 0, SCAT_E_WORKSPACE, "scat_bn_train_stats: workspace not 8-byte aligned");
     const int S = bn_splits(B, C);
     hipStream_t st = (hipStream_t)stream;
     static const int fused_min_c = diag_env_int("SCAT_BN_FUSED_MIN_C", 256);
@@ -1084,6 +1085,7 @@ extern "C" int scat_bn_bwd(const float* dy, const float* x, const float* y_out, 
                  "scat_bn_bwd: null pointer");
     SCAT_REQUIRE(B > 0 && C > 0 && HW > 0, SCAT_E_SHAPE, "scat_bn_bwd: non-positive dimension");
     SCAT_REQUIRE(ws && ws_bytes >= scat_bn_ws(B, C, HW), SCAT_E_WORKSPACE, "scat_bn_bwd: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 7) == 0, SCAT_E_WORKSPACE, "scat_bn_bwd: workspace not 8-byte aligned");
     const int S = bn_splits(B, C);
     double* part = (double*)ws;
     float* coef = bn_ws_coef(ws, C, S);
@@ -1159,6 +1161,7 @@ extern "C" int scat_bn_bwd_maxpool(const float* dy_pooled, const int8_t* idx, co
                  "scat_bn_bwd_maxpool: needs even H and W % 4 == 0");
     SCAT_REQUIRE((((uintptr_t)x | (uintptr_t)dx) & 15) == 0, SCAT_E_SHAPE, "scat_bn_bwd_maxpool: 16-B aligned tensors");
     SCAT_REQUIRE(ws && ws_bytes >= scat_bn_ws(B, C, H * W), SCAT_E_WORKSPACE, "scat_bn_bwd_maxpool: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 7) == 0, SCAT_E_WORKSPACE, "scat_bn_bwd_maxpool: workspace not 8-byte aligned");
     SCAT_REQUIRE(fits_i32((int64_t)B * C * H * W), SCAT_E_SHAPE, "scat_bn_bwd_maxpool: tensor exceeds 2^31 elements");
     const int S = bn_splits(B, C);
     double* part = (double*)ws;
@@ -1189,6 +1192,7 @@ extern "C" int scat_bn_bwd_pre(float* dy_g, const float* dy_add, const float* x,
                  "scat_bn_bwd_pre: null pointer");
     SCAT_REQUIRE(B > 0 && C > 0 && HW > 0, SCAT_E_SHAPE, "scat_bn_bwd_pre: non-positive dimension");
     SCAT_REQUIRE(ws && ws_bytes >= scat_bn_ws(B, C, HW), SCAT_E_WORKSPACE, "scat_bn_bwd_pre: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 7) == 0, SCAT_E_WORKSPACE, "scat_bn_bwd_pre: workspace not 8-byte aligned");
     SCAT_REQUIRE(!(y_mask && y_out), SCAT_E_ARG, "scat_bn_bwd_pre: pass the output OR its sign mask");
     SCAT_REQUIRE((HW & 3) == 0 && (((uintptr_t)dy_g | (uintptr_t)dy_add | (uintptr_t)x | (uintptr_t)y_out) & 15) == 0, SCAT_E_SHAPE,
                  "scat_bn_bwd_pre: needs HW % 4 == 0 and 16-B aligned tensors");
@@ -1305,6 +1309,7 @@ extern "C" int scat_layernorm_bwd(const float* dy, const float* x, const float* 
     }
     SCAT_REQUIRE(ws && ws_bytes >= scat_layernorm_bwd_ws(rows, dim), SCAT_E_WORKSPACE,
                  "scat_layernorm_bwd: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 3) == 0, SCAT_E_WORKSPACE, "scat_layernorm_bwd: workspace not 4-byte aligned");
     float* t = (float*)ws;
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, dy, x, gamma, mean, rstd, dx, t, rows,
                        dim);
@@ -1338,6 +1343,7 @@ extern "C" int scat_colsum_sliced(const float* x, float* out, int rows, int cols
     const int S = colsum2_slices(rows, cols);
     if (S <= 1) return scat_colsum(x, out, rows, cols, accumulate, stream);
     SCAT_REQUIRE(ws && ws_bytes >= scat_colsum_ws(rows, cols), SCAT_E_WORKSPACE, "scat_colsum_sliced: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 3) == 0, SCAT_E_WORKSPACE, "scat_colsum_sliced: workspace not 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(colsum2_part_kernel<false>, dim3(cdiv(cols, 16), S), dim3(1024), 0, st, x, (const float*)nullptr,
                        (float*)ws, rows, cols, cdiv(rows, S));

@@ -208,6 +208,7 @@ extern "C" int scat_performer_bwd(const float* dy, const float* kqv, const float
                  "scat_performer_bwd: null pointer");
     SCAT_REQUIRE(ws && ws_bytes >= scat_performer_bwd_ws(B, T, heads, e, m), SCAT_E_WORKSPACE,
                  "scat_performer_bwd: workspace too small");
+    SCAT_REQUIRE(((uintptr_t)ws & 3) == 0, SCAT_E_WORKSPACE, "scat_performer_bwd: workspace not 4-byte aligned");
     const int64_t bh = (int64_t)B * heads, rows = bh * T;
     float* dnum = (float*)ws;
     float* dD = dnum + bh * T * e;

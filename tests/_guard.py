@@ -9,7 +9,8 @@ stale data, and an output element the kernel skipped is still NaN afterwards.
     arena.check()                                               # guards bit for bit, outputs written and finite
 
 TorchProxy stands in for the ``torch`` module global of scat_amd.ops (monkeypatch.setattr(ops, "torch", proxy)): the
-outputs and workspaces the wrappers allocate with empty / empty_like / zeros / full are carved out of the arena too.
+outputs the wrappers allocate with empty / empty_like / zeros / full are carved out of the arena too, and
+exact_workspace() stands in for ops.workspace with buffers of exactly the requested size.
 Plain helper module: no fixtures, no pytest hooks."""
 from __future__ import annotations
 
@@ -214,6 +215,29 @@ class TorchProxy:
         if not self._dev_ok(device):
             return torch.full(size, fill_value, dtype=dtype, device=device, **kw)
         return self._carve(self._shape((size,)), dtype, "full").fill_(fill_value)
+
+
+def exact_workspace(proxy, stream=lambda: 0):
+    """A stand-in for scat_amd.ops.workspace(nbytes, device, slot) that carves EXACTLY nbytes (16 where 0 is asked for, so
+    that the pointer is not null) out of the proxy's arena as scratch: skew 0, the guard NaN as contents, a guard band
+    right behind the last requested byte.  Every request gets a fresh slot; only when the arena is full is a buffer of the
+    same (slot, stream, nbytes) handed out again.  Never a larger one."""
+    cache = {}
+
+    def workspace(nbytes, device, slot="default"):
+        n = int(nbytes) or 16
+        key = (slot, stream(), n)
+        try:
+            with proxy.scratch():
+                buf = proxy.empty(n, dtype=torch.uint8, device=device)
+        except MemoryError:
+            buf = cache.get(key)
+            if buf is None:
+                raise
+        cache[key] = buf
+        assert buf.numel() == n
+        return buf
+    return workspace
 
 
 def header_pointer_entry_points():

@@ -3,8 +3,11 @@ with the declared arity, error codes come back as exceptions.  No kernel is laun
 import ctypes
 import os
 import re
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))      # tests/test_gpu_guard.py (the WS table), tests/_guard.py
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -158,3 +161,108 @@ def test_bench_roofline_lookup_matches_profiles():
         inst = bench.instantiation_of(label, traffic)
         assert inst in traffic, (label, inst, sorted(traffic)[:8])
         assert traffic[inst]["hbm_bytes_per_launch"] > 0
+
+
+# ------------------------------------------------------------------ the workspace contract (tests/test_gpu_guard.py WS)
+#
+# Argument validation runs before any HIP call, so a call that is REFUSED never touches a device and the pointers can be
+# made-up integers: those tests run everywhere.  A call that passes validation goes on to launch; that outcome (-4 where no
+# device is visible, after the label was set) is only looked at where no device is visible — with one, the launch would
+# run on the made-up pointers.
+
+WS_PTR = 0x7000000      # 16-byte aligned, non-null, never dereferenced
+
+
+def _ws_rows():
+    import test_gpu_guard as G
+
+    return [n for n, r in G.WS.items() if r.where == "tests/test_cabi.py"]
+
+
+class _Entry:
+    """one row's entry point, called with made-up pointers; the product mode the row asks for is set around each call"""
+
+    def __init__(self, name):
+        import test_gpu_guard as G
+        from scat_amd._lib import lib
+
+        self.G, self.L, self.name, self.row = G, lib(), name, G.WS[name]
+        self.fn = getattr(self.L.cdll, name)        # the raw entry point: the code comes back, no exception
+
+    def need(self, shape=None):
+        args = self.G.ws_call_args(self.L, self.name, shape or self.row.shape, 0, 0)
+        return self.G.ws_query(self.L, self.name, dict(zip([an for _, an in self.L.protos[self.name][1]], args)))
+
+    def __call__(self, ws, ws_bytes, shape=None, null=()):
+        """-> (code, scat_last_error(), label before, label after)"""
+        saved = self.L.scat_get_math_mode()
+        if self.row.math is not None:
+            self.L.scat_set_math_mode(self.row.math)
+        try:
+            before = self.L.scat_last_kernel()
+            rc = int(self.fn(*self.G.ws_call_args(self.L, self.name, shape or self.row.shape, ws, ws_bytes, null)))
+            return rc, self.L.scat_last_error().decode(errors="replace"), before, self.L.scat_last_kernel()
+        finally:
+            self.L.scat_set_math_mode(saved)
+
+
+def _no_device():
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("a device is visible: a call that passes validation would launch on the made-up pointers")
+
+
+@pytest.mark.parametrize("name", _ws_rows())
+def test_short_absent_and_misaligned_workspaces_are_refused_on_the_host(name, built):
+    e = _Entry(name)
+    row, need = e.row, e.need()
+    assert need == row.nbytes > 0
+    refused = []
+    if row.short == "reject":
+        refused += [("one byte short", WS_PTR, need - 1, -3), ("absent", 0, need, -3)]
+    for off in (2, 4, 8):
+        if off % row.align and row.misaligned != "single_pass":
+            refused.append((f"ws % 16 == {off}", WS_PTR + off, need, CODES[row.misaligned]))
+    if row.short == "reject":
+        assert len(refused) >= 3
+    for what, ws, nbytes, code in refused:
+        rc, err, before, after = e(ws, nbytes)
+        assert rc == code, f"{name}, workspace {what}: {rc} ({err}), expected {code}"
+        assert name in err, (name, what, err)
+        assert before == after, f"{name}, workspace {what}: refused, yet the kernel label moved to {after}"
+
+
+CODES = {"SCAT_E_ARG": -2, "SCAT_E_WORKSPACE": -3}
+
+
+@pytest.mark.parametrize("name", _ws_rows())
+def test_sufficient_and_unused_workspaces_pass_validation(name, built):
+    """the other side of every refusal above: the exact size, every aligned offset and, where the row says the workspace
+    is unused, (0, 0) get as far as the launch"""
+    _no_device()
+    e = _Entry(name)
+    row, need = e.row, e.need()
+    launched = (lambda rc: rc >= 0) if name == "scat_wprep_jobs" else (lambda rc: rc == -4)     # (host only: no launch)
+    for off in (0, 4, 8, 16):
+        if off % row.align == 0:
+            rc, err, _, _ = e(WS_PTR + off, need)
+            assert launched(rc), f"{name}, ws % 16 == {off}, {need} bytes: {rc} ({err})"
+    if row.shape2 is not None and row.nbytes2:
+        rc, err, _, _ = e(WS_PTR, row.nbytes2, row.shape2)
+        assert launched(rc), (name, rc, err)
+        rc, err, _, _ = e(WS_PTR, row.nbytes2 - 1, row.shape2)
+        assert rc == (-4 if row.short == "single_pass" else -3), (name, rc, err)
+    if row.unused is not None:
+        over = dict(row.unused)
+        null = over.pop("null", ())
+        shape = dict(row.shape, **over)
+        assert over == {} or e.need(shape) == 0
+        rc, err, _, _ = e(0, 0, shape, null)
+        assert launched(rc), f"{name}: an unused workspace may be absent, yet {rc} ({err})"
+    if row.short == "single_pass":
+        # scat_gemm: no workspace, a short one or one that cannot hold floats -> one pass over K, the exact one -> the plan
+        for ws, nbytes, want in ((0, 0, "_split1"), (WS_PTR, need - 1, "_split1"), (0, need, "_split1"),
+                                 (WS_PTR + 2, need, "_split1"), (WS_PTR, need, "_split3")):
+            rc, err, _, label = e(ws, nbytes)
+            assert rc == -4 and label.decode().endswith(want), (ws, nbytes, rc, err, label)

@@ -15,11 +15,15 @@ placements agree with each other within the same gate.
 What a skewed operand does is written down per case BEFORE any run, from the host code of the entry point: ``compute``
 (a fallback kernel, or a kernel that never needed the alignment) or the SCAT_E_* code a specialised entry point rejects
 with.  A call through a dispatching ``ops`` wrapper must compute; only ``direct`` cases (a specialised entry point, or a
-wrapper that is nothing but that entry point) may reject.  Workspaces come from ops.workspace / WeightPrep, which the
-allocator always aligns: they are guarded but never skewed.
+wrapper that is nothing but that entry point) may reject.  Workspaces are allocator-aligned in the product
+(ops.workspace, WeightPrep): here they are guarded, never skewed, and EXACTLY as large as the caller asked for — which is
+what the scat_*_ws query returned — so a query that promises less than its launch writes, or a launch that ignores
+ws_bytes, damages the guard behind the workspace.  (ops.workspace itself never hands out less than 1 MiB.)
 
-CASES / EXEMPT are read by tests/test_guard_harness.py (no GPU): every pointer-taking prototype of include/scat_hip.h is
-in one of them.  In placement A each case also checks that the entry points it names were really called."""
+CASES / EXEMPT / WS are read by tests/test_guard_harness.py (no GPU): every pointer-taking prototype of
+include/scat_hip.h is in one of the first two, every prototype with a ws_bytes argument (both headers) has a row in WS.
+In placement A each case also checks that the entry points it names were really called, and that each of them with a row
+in WS was handed, at least once, a workspace of exactly its queried size with that size non-zero."""
 import contextlib
 import ctypes
 import math
@@ -80,19 +84,173 @@ def v4(a):
     return a.view(1, -1, 1, 1)
 
 
+# ------------------------------------------------------------------------------------------ the workspace contract
+
+class Ws:
+    """What one entry point with a (ws, ws_bytes) pair promises about it, written down from its host code before any run.
+    query / qargs: the scat_*_ws function that sizes ws and its arguments from the entry point's own (named) ones.
+    align: bytes, the widest access the kernels make to ws (16: 16-byte stores of re-laid weights / 16-byte loads; 8:
+    doubles and 64-bit atomics; 4: floats only).
+    short: what ws_bytes = query - 1, or a null ws, does: "reject" (SCAT_E_WORKSPACE) or "single_pass" (scat_gemm).
+    misaligned: the code for a ws that is not a multiple of ``align`` ("single_pass": scat_gemm again).
+    shape -> nbytes: the smallest arguments of interest and the bytes the query returns there; shape2 -> nbytes2: the other
+    side of the branch in the query's plan (``branch`` names it).
+    unused: argument overrides ("null": pointers passed as null) under which ws is not looked at and (0, 0) is fine.
+    math: the product mode the entry point insists on (the weight gradient: the mode in which its first candidate runs).
+    build: shape -> the arguments that are host memory.  where: the module that tests the refusals, if not test_cabi."""
+
+    def __init__(self, query, qargs, align, shape, nbytes, short="reject", misaligned="SCAT_E_WORKSPACE", shape2=None,
+                 nbytes2=None, branch=None, unused=None, null=(), math=None, build=None, where="tests/test_cabi.py"):
+        self.query, self.qargs, self.align, self.shape, self.nbytes = query, qargs, align, shape, nbytes
+        self.short, self.misaligned, self.shape2, self.nbytes2, self.branch = short, misaligned, shape2, nbytes2, branch
+        self.unused, self.null, self.math, self.build, self.where = unused, tuple(null), math, build, where
+
+
+def _group_problems(shape):
+    """scat_gemm_group's HOST array for the (M_q, N_q, K) of shape["problems"], operands laid out as a weight gradient"""
+    from scat_amd.ops import _GemmProblem
+
+    dims = shape["problems"]
+    arr = (_GemmProblem * len(dims))()
+    for q, (M, N, K) in enumerate(dims):
+        arr[q] = _GemmProblem(0x100000 * (3 * q + 1), 1, M, 0x100000 * (3 * q + 2), N, 1, 0x100000 * (3 * q + 3), N, 1, M, N, K)
+    return dict(problems=arr, n=len(dims))
+
+
+def _wprep_host(shape):
+    jobs, nj = ctypes.create_string_buffer(4 * 256), ctypes.c_int(0)
+    return dict(jobs_out=jobs, njobs_out=ctypes.byref(nj), max_jobs=4)
+
+
+def _wprep_query(a):
+    """the query of the entry point that will be handed this buffer (include/scat_hip.h SCAT_WPREP_*)"""
+    k = a["kind"]
+    if k in (0, 1):
+        return ("scat_conv1x1_s1_ws", (a["Cout"], a["Cin"]) if k == 0 else (a["Cin"], a["Cout"]))
+    if k in (2, 3):
+        return ("scat_conv3x3_s1_ws", (a["Cout"], a["Cin"]))
+    if k == 4:
+        return ("scat_conv2d_fwd_split_ws", (a["Cout"], a["Cin"], a["KH"], a["KW"]))
+    return ("scat_conv2d_dgrad_s2_ws", (a["Cin"], a["Cout"], a["KH"], a["KW"]))
+
+
+_BN_Q = lambda a: (a["B"], a["C"], a["HW"])
+_BN_ROW = dict(shape=dict(B=4, C=32, HW=49), nbytes=4608, shape2=dict(B=12, C=200, HW=729), nbytes2=73600,
+               branch="bn_splits: 4 slots per channel, limited by B | 11, limited by 2048 / C")
+_GEMM_STRIDES = lambda M, N, K: dict(M=M, N=N, K=K, a_si=K, a_sk=1, b_sk=N, b_sj=1, c_si=N, c_sj=1)
+_WG = lambda B, Cin, H, W, Cout, k, s: dict(B=B, Cin=Cin, H=H, W=W, Cout=Cout, KH=k, KW=k, stride=s, pad=k // 2)
+
+# one row per prototype with a ws_bytes argument, include/scat_hip.h then include/scat_eval.h, in header order
+WS = {
+    "scat_conv2d_dgrad_s2": Ws("scat_conv2d_dgrad_s2_ws", lambda a: (a["Cin"], a["Cout"], a["KH"], a["KW"]), 16,
+                               dict(B=2, Cin=32, H=13, W=9, Cout=72, KH=3, KW=3, pad=1), 138240),
+    "scat_conv3x3_s1": Ws("scat_conv3x3_s1_ws", lambda a: (a["Cout"], a["Cin"]), 16,
+                          dict(B=3, Cin=36, H=7, W=7, Cout=64), 165888),
+    "scat_conv2d_fwd_split": Ws("scat_conv2d_fwd_split_ws", lambda a: (a["Cout"], a["Cin"], a["KH"], a["KW"]), 16,
+                                dict(B=2, Cin=32, H=13, W=9, Cout=72, KH=3, KW=3, stride=2, pad=1), 124416, math=1),
+    "scat_vit_qkv_attn_fwd": Ws("scat_vit_qkv_attn_fwd_ws", lambda a: (a["dim"], a["heads"]), 16,
+                                dict(B=5, n=16, dim=200, heads=2), 479232, math=1),
+    "scat_conv7x7_s2_fwd_split": Ws("scat_conv7x7_s2_fwd_split_ws", lambda a: (a["Cout"],), 16,
+                                    dict(B=3, H=38, W=54, Cout=64), 73728, math=1),
+    "scat_conv7x7_s2_wgrad_split": Ws("scat_conv7x7_s2_wgrad_split_ws", lambda a: (a["B"], a["H"], a["W"]), 16,
+                                      dict(B=2, H=22, W=32, Cout=64), 225792, shape2=dict(B=4, H=1544, W=32, Cout=64),
+                                      nbytes2=23256576, math=1,
+                                      branch="stem_wg_rows_per_wg: 4 rows per workgroup (22 rows) | 5 (3088 rows > 4 * 768)"),
+    # its one alignment test covers w, src and ws and answers SCAT_E_ARG
+    "scat_conv1x1_s1": Ws("scat_conv1x1_s1_ws", lambda a: (a["M"], a["C"]), 16, dict(B=2, C=48, HW=117, M=80), 23040,
+                          misaligned="SCAT_E_ARG"),
+    "scat_conv1x1_planes": Ws("scat_conv1x1_s1_ws", lambda a: (a["M"], a["C"]), 16, dict(B=3, C=32, HW=81, M=64), 12288,
+                              math=1),
+    "scat_wprep_jobs": Ws(None, _wprep_query, 16, dict(kind=0, Cout=80, Cin=48, KH=1, KW=1, pad=0, blk0=0), 23040,
+                          build=_wprep_host),
+    # the engine is chosen per call from one candidate list and only its own slabs are asked for; the row's shape is one
+    # whose first candidate in product mode 1 (the rows engine) is also the largest, so query - 1 is short for it
+    "scat_conv2d_wgrad": Ws("scat_conv2d_wgrad_ws", lambda a: tuple(a[k] for k in ("B", "Cin", "H", "W", "Cout", "KH", "KW",
+                                                                                   "stride", "pad")), 4,
+                            _WG(5, 32, 7, 40, 64, 3, 1), 368640, unused=_WG(2, 48, 9, 13, 80, 1, 1), math=1),
+    "scat_gemm": Ws("scat_gemm_ws", lambda a: (a["M"], a["N"], a["K"]), 4, _GEMM_STRIDES(84, 588, 784), 592704,
+                    short="single_pass", misaligned="single_pass", shape2=_GEMM_STRIDES(84, 3, 147), nbytes2=0,
+                    null=("bias",), branch="gemm_plan: 3 K-slices | 1 (K < 512: no slabs, no workspace)"),
+    "scat_gemm_group": Ws("scat_gemm_group_ws", lambda a: (a["problems"], a["n"]), 16,
+                          dict(problems=[(70, 33, 600), (3, 147, 600)]), 22008, build=_group_problems,
+                          shape2=dict(problems=[(70, 33, 300), (3, 147, 300)]), nbytes2=0,
+                          branch="group_splits: 2 K-slices | 1 (K < 512)"),
+    "scat_gemm_split": Ws("scat_gemm_split_ws", lambda a: (a["M"], a["K"]), 16, dict(M=130, N=70, K=66), 62400, math=1,
+                          null=("bias_n",)),
+    "scat_bn_train_stats": Ws("scat_bn_ws", _BN_Q, 8, **_BN_ROW),
+    "scat_bn_bwd": Ws("scat_bn_ws", _BN_Q, 8, null=("y_out", "y_mask"), **_BN_ROW),
+    "scat_bn_bwd_maxpool": Ws("scat_bn_ws", lambda a: (a["B"], a["C"], a["H"] * a["W"]), 8, dict(B=5, C=70, H=10, W=8),
+                              12320, shape2=dict(B=13, C=200, H=4, W=8), nbytes2=73600, branch=_BN_ROW["branch"]),
+    "scat_bn_bwd_pre": Ws("scat_bn_ws", _BN_Q, 8, dict(B=3, C=48, HW=36), 5376, shape2=dict(B=13, C=200, HW=36),
+                          nbytes2=73600, null=("y_out", "y_mask"), branch=_BN_ROW["branch"]),
+    "scat_conv1x1_s1_bnb": Ws("scat_conv1x1_s1_ws", lambda a: (a["Cin"], a["Cout"]), 16, dict(B=3, Cin=64, HW=144, Cout=256),
+                              98304, math=1),
+    "scat_conv1x1_wgrad_bnb": Ws("scat_conv1x1_wgrad_bnb_ws", lambda a: (a["B"], a["Cin"], a["HW"], a["Cout"]), 4,
+                                 dict(B=2, Cin=128, HW=252, Cout=128), 131072, unused=dict(B=3, Cin=64, HW=144, Cout=256),
+                                 math=1),
+    "scat_layernorm_bwd": Ws("scat_layernorm_bwd_ws", lambda a: (a["rows"], a["dim"]), 4, dict(rows=40, dim=196), 32928,
+                             shape2=dict(rows=21400, dim=196), nbytes2=16901472, unused=dict(null=("dgamma", "dbeta")),
+                             branch="colsum2_slices: 1 slice | 79 (rows * dim >= 1 << 22)"),
+    "scat_performer_bwd": Ws("scat_performer_bwd_ws", lambda a: tuple(a[k] for k in ("B", "T", "heads", "e", "m")), 4,
+                             dict(B=2, T=21, heads=8, e=49, m=65), 362560),
+    "scat_colsum_sliced": Ws("scat_colsum_ws", lambda a: (a["rows"], a["cols"]), 4, dict(rows=24001, cols=196), 61936,
+                             shape2=dict(rows=300, cols=61), nbytes2=0, unused=dict(rows=300, cols=61),
+                             branch="colsum2_slices: 79 slices | 1 (rows * cols < 1 << 22: the call is scat_colsum)"),
+    "scat_regressor_bwd": Ws("scat_regressor_bwd_ws", lambda a: (a["B"], a["F"], a["P"], a["iters"]), 4,
+                             dict(B=5, F=196, P=61, iters=3), 4880),
+    # include/scat_eval.h: a null or misaligned ws is SCAT_E_ARG there, a short one SCAT_E_WORKSPACE
+    "scat_eval_frame_mask": Ws("scat_eval_frame_mask_ws", lambda a: (a["B"], a["n"]), 8, dict(B=3, n=150528), 456,
+                               misaligned="SCAT_E_ARG", where="tests/test_eval.py"),
+    "scat_eval_accumulate": Ws("scat_eval_accumulate_ws", lambda a: (a["B"], a["T"]), 8, dict(B=5, T=7, ld_gt=105), 232,
+                               misaligned="SCAT_E_ARG", null=("keep", "per_sample", "aligned"), where="tests/test_eval.py"),
+}
+
+
+def ws_query(L, name, args):
+    """the bytes row WS[name]'s query returns for the entry point's named arguments"""
+    row = WS[name]
+    q, qa = (row.query, row.qargs(args)) if row.query else row.qargs(args)
+    return int(getattr(L, q)(*qa))
+
+
+def ws_call_args(L, name, shape, ws, ws_bytes, null=()):
+    """positional arguments of entry point ``name`` at ``shape`` for a call that is to stop in the host code (no GPU):
+    distinct non-null 16-byte-aligned integers as pointers (null for row.null and ``null``), 0 for flags and the stream"""
+    row = WS[name]
+    vals = dict(shape)
+    if row.build:
+        vals.update(row.build(shape))
+    out = []
+    for n, (ty, an) in enumerate(L.protos[name][1]):
+        if an in ("ws", "ws_bytes"):
+            out.append(ws if an == "ws" else ws_bytes)
+        elif an in vals:
+            out.append(vals[an])
+        elif ty is ctypes.c_void_p:
+            out.append(0 if an in row.null or an in null or an == "stream" else 0x100000 * (n + 1))
+        else:
+            out.append(0.125 if ty is ctypes.c_float else 0)
+    return out
+
+
 class _Recorder:
-    """scat_amd._lib.lib() with the names of the entry points that were called"""
+    """scat_amd._lib.lib() with the names of the entry points that were called and, for those with a row in WS, the
+    (ws_bytes handed in, bytes the row's query returns for the call's own arguments) of every call"""
 
     def __init__(self, real):
-        self._real, self.called = real, set()
+        self._real, self.called, self.ws = real, set(), {}
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
         if not name.startswith("scat_"):
             return fn
+        names = [an for _, an in self._real.protos[name][1]] if name in WS else None
 
         def call(*a):
             self.called.add(name)
+            if names is not None:
+                args = dict(zip(names, a))
+                self.ws.setdefault(name, []).append((int(args["ws_bytes"]), ws_query(self._real, name, args)))
             return fn(*a)
         return call
 
@@ -150,9 +308,10 @@ def _conv_ref(x, w, bias, s, p, sc=None, sh=None):
     return F.conv2d(a, w.double(), None if bias is None else bias.double(), stride=s, padding=p)
 
 
-def _conv_family(t, B, cin, cout, H, W, k, s, p, seed, bias=True, fwd_label=None, wg_label=None):
+def _conv_family(t, B, cin, cout, H, W, k, s, p, seed, bias=True, fwd_label=None, wg_label=None, wg_deep=None):
     """forward (+bias), forward with the fused relu(bn(x)) operand, data gradient plain and accumulating (from the original
-    weights), weight gradient plain and with the fused operand"""
+    weights), weight gradient plain and with the fused operand.  wg_deep = (B, H, W): the weight gradient once more over
+    enough pixels for scat_conv2d_wgrad_ws to be non-zero (the family's own plane needs no slabs)"""
     ops = t.ops
     x = t.once("x", lambda: R(seed, (B, cin, H, W)))
     w = t.once("w", lambda: R(seed + 1, (cout, cin, k, k), std=(2.0 / (cin * k * k)) ** 0.5))
@@ -186,11 +345,20 @@ def _conv_family(t, B, cin, cout, H, W, k, s, p, seed, bias=True, fwd_label=None
         a = lambda: F.relu(x.double() * v4(sc.double()) + v4(sh.double()))
         t.out("dw_tf", ops.conv2d_wgrad(dyg, xg, tuple(w.shape), s, p, scg, shg, True),
               lambda: torch.nn.grad.conv2d_weight(a(), tuple(w.shape), dy.double(), stride=s, padding=p))
+    if wg_deep:
+        _wgrad_deep(t, cin, cout, k, s, p, seed, *wg_deep)
+
+
+def _wgrad_deep(t, cin, cout, k, s, p, seed, B, H, W):
+    x = t.once("x_deep", lambda: R(seed + 7, (B, cin, H, W)))
+    dy = t.once("dy_deep", lambda: R(seed + 8, (B, cout) + tuple(t.ops.conv_out_hw(H, W, k, s, p))))
+    t.out("dw_deep", t.ops.conv2d_wgrad(t.inp(dy, "dy_deep"), t.inp(x, "x_deep"), (cout, cin, k, k), s, p),
+          lambda: torch.nn.grad.conv2d_weight(x.double(), (cout, cin, k, k), dy.double(), stride=s, padding=p))
 
 
 def _pw(t, *shape, seed):
     t.mp.setattr(t.ops, "PW_MIN_C", 0)
-    _conv_family(t, *shape, 1, 1, 0, seed, fwd_label="conv1x1_split" if t.math else "conv1x1_pw")
+    _conv_family(t, *shape, 1, 1, 0, seed, fwd_label="conv1x1_split" if t.math else "conv1x1_pw", wg_deep=(6, 13, 13))
 
 
 # the pointwise (weights-in-registers) kernel: scalar and vector pixel staging, ragged row / pixel tiles, both product modes,
@@ -216,12 +384,14 @@ def _c3(t):
 # workspace, the epilogue stores per element: no alignment need -> compute everywhere
 @case("conv3x3_9x13", ("scat_conv3x3_s1", "scat_conv2d_wgrad"), 2e-5, fills=("nan", "big"), maths=(0, 1), skews=(2, 3))
 def _c4(t):
-    _conv_family(t, 2, 20, 72, 9, 13, 3, 1, 1, 130, bias=False, fwd_label="conv3x3_split" if t.math else "conv3x3_halo")
+    _conv_family(t, 2, 20, 72, 9, 13, 3, 1, 1, 130, bias=False, fwd_label="conv3x3_split" if t.math else "conv3x3_halo",
+                 wg_deep=(6, 13, 13))
 
 
 @case("conv3x3_7x7", ("scat_conv3x3_s1", "scat_conv2d_wgrad"), 2e-5, maths=(0, 1))
 def _c5(t):
-    _conv_family(t, 3, 36, 64, 7, 7, 3, 1, 1, 140, bias=False, fwd_label="conv3x3_split" if t.math else "conv3x3_halo")
+    _conv_family(t, 3, 36, 64, 7, 7, 3, 1, 1, 140, bias=False, fwd_label="conv3x3_split" if t.math else "conv3x3_halo",
+                 wg_deep=(6, 13, 13))
 
 
 # stride 2 on the split-operand taps kernel (forward) and the parity-class data gradient, odd planes
@@ -231,11 +401,12 @@ def _c6(t):
     _conv_family(t, 2, 32, 72, 13, 9, 3, 2, 1, 150)
     if t.aligned:
         assert "_s2_split_" in t.label(), t.label()
+    _wgrad_deep(t, 32, 72, 3, 2, 1, 150, 4, 27, 27)
 
 
 @case("conv_s2_1x1_7x7", ("scat_conv2d_fwd_split", "scat_conv2d_dgrad_s2", "scat_conv2d_wgrad"), 2e-5, maths=(1,))
 def _c7(t):
-    _conv_family(t, 3, 48, 64, 7, 7, 1, 2, 0, 160)
+    _conv_family(t, 3, 48, 64, 7, 7, 1, 2, 0, 160, wg_deep=(8, 28, 28))
 
 
 @case("dgrad_s2_odd", ("scat_conv2d_dgrad_s2",), 2e-5, maths=(0, 1))
@@ -278,14 +449,16 @@ def _c10(t):
 # code its one alignment test raises; x and dw are not looked at (4-byte loads, per-element stores) -> O computes
 @case("stem_wgrad_direct", ("scat_conv7x7_s2_wgrad_split",), 2e-5, expect={"S": "SCAT_E_WORKSPACE"}, direct=True, maths=(1,))
 def _c11(t):
-    B, H, W = 2, 22, 32
-    x = t.once("x", lambda: R(200, (B, 3, H, W)))
-    dy = t.once("dy", lambda: R(201, (B, 64, 11, 16)))
-    xg, dyg = t.inp(x, "x"), t.inp(dy, "dy")
-    dw = t.buf((64, 3, 7, 7), "dw")
-    ws = t.ops.workspace(t.lib.scat_conv7x7_s2_wgrad_split_ws(B, H, W), xg.device, "stem")
-    t.lib.scat_conv7x7_s2_wgrad_split(P(dyg), P(xg), P(dw), B, H, W, 64, P(ws), ws.numel(), t.stream())
-    t.out("dw", dw, lambda: torch.nn.grad.conv2d_weight(x.double(), (64, 3, 7, 7), dy.double(), stride=2, padding=3))
+    # 22 output rows: 4 rows per workgroup; 3088 rows: 5 (the other value of stem_wg_rows_per_wg, 618 slabs)
+    for tag, (B, H, W) in (("", (2, 22, 32)), ("_tall", (4, 1544, 32))):
+        x = t.once("x" + tag, lambda: R(200, (B, 3, H, W)))
+        dy = t.once("dy" + tag, lambda: R(201, (B, 64, H // 2, W // 2)))
+        xg, dyg = t.inp(x, "x" + tag), t.inp(dy, "dy" + tag)
+        dw = t.buf((64, 3, 7, 7), "dw" + tag)
+        ws = t.ops.workspace(t.lib.scat_conv7x7_s2_wgrad_split_ws(B, H, W), xg.device, "stem")
+        t.lib.scat_conv7x7_s2_wgrad_split(P(dyg), P(xg), P(dw), B, H, W, 64, P(ws), ws.numel(), t.stream())
+        t.out("dw" + tag, dw,
+              lambda: torch.nn.grad.conv2d_weight(x.double(), (64, 3, 7, 7), dy.double(), stride=2, padding=3))
 
 
 # row-walking 3x3 weight gradient (csrc/conv_wgrad_rows.hip): taken only for aligned dy and x (its host test), else the
@@ -392,7 +565,7 @@ def _c13c(t):
 @case("conv_generic", ("scat_conv2d_fwd", "scat_conv2d_dgrad", "scat_conv2d_wt", "scat_conv2d_wgrad"), 2e-5,
       fills=("nan", "big"), maths=(0, 1))
 def _c14(t):
-    _conv_family(t, 5, 20, 130, 9, 9, 1, 1, 0, 230)
+    _conv_family(t, 5, 20, 130, 9, 9, 1, 1, 0, 230, wg_deep=(6, 13, 13))
     x = t.once("x3", lambda: R(236, (4, 3, 6, 5)))
     w = t.once("w3", lambda: R(237, (5, 3, 3, 3), std=0.3))
     dy = t.once("dy3", lambda: R(238, (4, 5, 6, 5)))
@@ -615,6 +788,13 @@ def _b4(t):
     _bn_block(t, 3, 256, 14, 14, 330)
 
 
+# C = 200, B = 12: 2048 / C limits the slots per channel (11 < B; above, B does); HW % 4 != 0 and B * HW > 8192: scalar
+# kernels, the two-pass backward with its slots and claim words
+@case("bn_12x200x27x27", _BN_SYMS, 2e-5)
+def _b4b(t):
+    _bn_block(t, 12, 200, 27, 27, 335)
+
+
 @case("bn_apply_shortcut", ("scat_bn_apply",), 1e-6)
 def _b5(t):
     """relu(bn3(c3) + bnd(cd)): the shortcut's BatchNorm folded into the add, vector and scalar planes"""
@@ -656,9 +836,18 @@ def _b6(t):
 # skewed dy_g / dy_add / x / y_out; dy_g is also what it writes, so O rejects too
 @case("bn_bwd_pre", ("scat_bn_bwd_pre",), 2e-5, expect={"S": "SCAT_E_SHAPE", "O": "SCAT_E_SHAPE"}, direct=True)
 def _b7(t):
-    B, C, H, W = 3, 48, 6, 6
-    x, gamma, beta, res, dy, rm, rv = _bn_inputs(t, B, C, H, W, 360)
-    add = t.once("add", lambda: R(367, (B, C, H, W)))
+    _bn_pre(t, 3, 48, 6, 6, 360)
+
+
+# the same with 2048 / C limiting the slots per channel (C = 200, B = 13: 11 slots; above, B = 3 does)
+@case("bn_bwd_pre_wide", ("scat_bn_bwd_pre",), 2e-5, expect={"S": "SCAT_E_SHAPE", "O": "SCAT_E_SHAPE"}, direct=True)
+def _b7b(t):
+    _bn_pre(t, 13, 200, 6, 6, 365)
+
+
+def _bn_pre(t, B, C, H, W, seed):
+    x, gamma, beta, res, dy, rm, rv = _bn_inputs(t, B, C, H, W, seed)
+    add = t.once("add", lambda: R(seed + 7, (B, C, H, W)))
     ref = lambda: _bn_ref(t, x, gamma, beta, res, dy, rm, rv)
     f32 = lambda k: t.once("f32" + k, lambda: ref()[k].float())
     yout = t.inp(t.once("yout", lambda: ref()["y"].float()), "y_out")
@@ -678,10 +867,19 @@ def _b7(t):
 @case("bn_bwd_maxpool", ("scat_bn_bwd_maxpool", "scat_maxpool3x3s2_fwd", "scat_bn_train_stats"), 2e-5,
       expect={"S": "SCAT_E_SHAPE", "O": "SCAT_E_SHAPE"}, direct=True, fills=("nan", "big"))
 def _b8(t):
-    B, C, H, W = 5, 70, 10, 8
-    x = t.once("x", lambda: R(370, (B, C, H, W)) * 1.2 + 0.1)
-    gamma, beta = t.once("gamma", lambda: U(371, (C,), 0.5, 1.5)), t.once("beta", lambda: U(372, (C,), -0.3, 0.3))
-    dy = t.once("dy", lambda: R(373, (B, C, H // 2, W // 2)))
+    _bn_maxpool(t, 5, 70, 10, 8, 370)
+
+
+@case("bn_bwd_maxpool_wide", ("scat_bn_bwd_maxpool", "scat_maxpool3x3s2_fwd", "scat_bn_train_stats"), 2e-5,
+      expect={"S": "SCAT_E_SHAPE", "O": "SCAT_E_SHAPE"}, direct=True)
+def _b8b(t):
+    _bn_maxpool(t, 13, 200, 4, 8, 375)
+
+
+def _bn_maxpool(t, B, C, H, W, seed):
+    x = t.once("x", lambda: R(seed, (B, C, H, W)) * 1.2 + 0.1)
+    gamma, beta = t.once("gamma", lambda: U(seed + 1, (C,), 0.5, 1.5)), t.once("beta", lambda: U(seed + 2, (C,), -0.3, 0.3))
+    dy = t.once("dy", lambda: R(seed + 3, (B, C, H // 2, W // 2)))
     xg, gg, bg = t.inp(x, "x"), t.inp(gamma, "gamma"), t.inp(beta, "beta")
     mean, invstd, scale, shift = t.ops.bn_train_stats(xg, gg, bg, t.acc(torch.zeros(C), "rm"), t.acc(torch.ones(C), "rv"))
     y, idx = t.ops.maxpool_fwd(xg, scale, shift, True)
@@ -723,6 +921,13 @@ def _b9(t):
         assert "_bnb" in t.label(), t.label()
     t.out("dw", dw, lambda: torch.einsum("nop,nip->oi", dz().flatten(2), F.relu(a2.double() * v4(sc.double())
                                                                                  + v4(sh.double())).flatten(2)).view(cout, cin, 1, 1))
+    # that weight gradient needs no slabs (its query is 0); 128 -> 128 over 2 x 252 pixels does (131 072 bytes)
+    B, cin, cout, H, W = 2, 128, 128, 14, 18
+    g2, z2 = t.once("g2", lambda: R(388, (B, cout, H, W))), t.once("z2", lambda: R(389, (B, cout, H, W)))
+    c2, x2 = t.once("c2", lambda: U(378, (3, cout), -0.5, 0.5)), t.once("x2", lambda: R(379, (B, cin, H, W)))
+    dw2 = t.ops.conv1x1_wgrad_bnb(t.inp(g2, "g2"), t.inp(z2, "z2"), t.inp(c2, "coef3_2"), t.inp(x2, "x2"), (cout, cin, 1, 1))
+    dz2 = lambda: v4(c2[0].double()) * g2.double() + v4(c2[1].double()) * z2.double() + v4(c2[2].double())
+    t.out("dw2", dw2, lambda: torch.einsum("nop,nip->oi", dz2().flatten(2), x2.double().flatten(2)).view(cout, cin, 1, 1))
 
 
 def bn3_reference(c3, res_sign, gamma, mean, invstd, g_old, dc1, w1):
@@ -887,7 +1092,8 @@ def _p6(t):
 
 @case("layernorm", ("scat_layernorm_fwd", "scat_layernorm_bwd"), 1e-5, skews=(2, 3))
 def _t1(t):
-    for rows, dim in ((7, 50), (40, 196)):
+    # (21400 x 196 >= 1 << 22: the parameter sums in 79 row slices, their partials behind the rows * dim floats of ws)
+    for rows, dim in ((7, 50), (40, 196), (21400, 196)):
         key = f"{rows}"
         x = t.once("x" + key, lambda: R(500 + rows, (rows, dim)) * 2 + 0.3)
         gm, bt = t.once("g" + key, lambda: U(501, (dim,), 0.7, 1.3)), t.once("b" + key, lambda: U(502, (dim,), -0.2, 0.2))
@@ -1021,7 +1227,8 @@ def _t7(t):
 # the fp32 GEMM engine picks 16-byte loaders per operand from its pointer and strides (csrc/linear.hip av / bv)
 @case("linear_gemm", ("scat_gemm",), 2e-5, skews=(2, 3))
 def _t8(t):
-    for M, N, K in ((84, 3, 147), (300, 200, 147), (7, 66, 1090)):
+    # (K = 147: one pass.  7 x 66 x 1090: 4 K-slices forward.  84 x 588 x 784: 3 forward, 3 for the input gradient)
+    for M, N, K in ((84, 3, 147), (300, 200, 147), (7, 66, 1090), (84, 588, 784)):
         key = f"{M}x{N}"
         x = t.once("x" + key, lambda: R(570 + M, (M, K)))
         w = t.once("w" + key, lambda: R(571 + M, (N, K), std=K ** -0.5))
@@ -1036,6 +1243,33 @@ def _t8(t):
         t.out("ya" + key, acc, lambda: x.double() @ w.double().t() + base.double())
         t.out("dx" + key, t.ops.linear_dgrad(dyg, wg), lambda: dy.double() @ w.double())
         t.out("dw" + key, t.ops.linear_wgrad(dyg, xg), lambda: dy.double().t() @ x.double())
+
+
+# scat_gemm does not reject a missing or short workspace: it drops its K-slices and runs one pass, whose epilogue applies
+# bias and accumulate in the contraction kernel (the sliced form applies them in the reduce).  84 x 588 x 784: 3 slices,
+# 592 704 bytes.  (0, 0) and a buffer one byte short end in _split1, the exact one in _split3; the short buffer is real
+# and guarded, so a launch that believed the plan instead of ws_bytes would be seen.
+@case("gemm_without_workspace", ("scat_gemm",), 2e-5, direct=True)
+def _t8b(t):
+    M, N, K = 84, 588, 784
+    a = t.once("a", lambda: R(575, (M, K)))
+    b = t.once("b", lambda: R(576, (K, N), std=K ** -0.5))
+    bias = t.once("bias", lambda: R(577, (N,)))
+    base = t.once("base", lambda: R(578, (M, N)))
+    ag, bg, biasg = t.inp(a, "a"), t.inp(b, "b"), t.inp(bias, "bias")
+    need = int(t.lib.scat_gemm_ws(M, N, K))
+    assert need == 3 * M * N * 4
+    ref = lambda: a.double() @ b.double()
+    for tag, nbytes, want in (("none", 0, "_split1"), ("short", need - 1, "_split1"), ("exact", need, "_split3")):
+        ws, nb = _exact_ws(t, nbytes)
+        c = t.buf((M, N), "c_" + tag)
+        t.lib.scat_gemm(P(ag), K, 1, P(bg), N, 1, P(c), N, 1, M, N, K, P(biasg), 2, 0, ws, nb, t.stream())
+        assert t.label().endswith(want), (tag, t.label())
+        t.out("c_" + tag, c, lambda: ref() + bias.double())
+        acc = t.acc(base, "acc_" + tag)
+        t.lib.scat_gemm(P(ag), K, 1, P(bg), N, 1, P(acc), N, 1, M, N, K, 0, 0, 1, ws, nb, t.stream())
+        assert t.label().endswith(want), (tag, t.label())
+        t.out("acc_" + tag, acc, lambda: ref() + base.double())
 
 
 # the same contraction on the pointwise split kernel: b by 4-byte buffer loads, a re-laid into the workspace -> no
@@ -1060,7 +1294,8 @@ def _t9(t):
 
 @case("gemm_group", ("scat_gemm_group_ws", "scat_gemm_group"), 2e-5)
 def _t10(t):
-    for M, dims in ((300, [(70, 33), (129, 64), (64, 200), (3, 147)]), (84, [(3, 147), (147, 196)])):
+    # (M is the contraction length: 300 and 84 tokens run in one pass, 600 in 2 K-slices through the workspace)
+    for M, dims in ((300, [(70, 33), (129, 64), (64, 200), (3, 147)]), (84, [(3, 147), (147, 196)]), (600, [(70, 33), (3, 147)])):
         pairs, cpu = [], []
         for j, (N, K) in enumerate(dims):
             dy = t.once(f"dy{M}_{j}", lambda: R(590 + M + j, (M, N)))
@@ -1085,13 +1320,19 @@ def _t11(t):
 
 @case("colsum", ("scat_colsum", "scat_colsum_sliced", "scat_colsum_group"), 1e-5)
 def _t12(t):
-    for rows, cols in ((300, 61), (22000, 196)):       # (the second: row slices — 4.3 M elements, above the 2^22 switch)
+    # (the second: row slices — 4.3 M elements, above the 2^22 switch; the third: 79 ragged slices of 304 rows)
+    for rows, cols in ((300, 61), (22000, 196), (24001, 196)):
         x = t.once(f"x{rows}", lambda: R(610 + cols, (rows, cols), mean=0.25))
         xg = t.inp(x, f"x{rows}")
         t.out(f"s{rows}", t.ops.colsum(xg), lambda: x.double().sum(0))
         acc = t.acc(torch.ones(cols), f"acc{rows}")
         t.ops.colsum(xg, out=acc, accumulate=True)
         t.out(f"sa{rows}", acc, lambda: x.double().sum(0) + 1.0)
+    # one slice: the entry point is scat_colsum, its workspace unused (query 0) and absent
+    x300, small = t.once("x300", lambda: R(610 + 61, (300, 61), mean=0.25)), t.buf((61,), "direct300")
+    assert t.lib.scat_colsum_ws(300, 61) == 0
+    t.lib.scat_colsum_sliced(P(t.inp(x300, "x300_direct")), P(small), 300, 61, 0, 0, 0, t.stream())
+    t.out("direct300", small, lambda: x300.double().sum(0))
     xs = [t.once(f"g{j}", lambda: R(620 + j, shp, mean=0.1 * j)) for j, shp in enumerate([(77, 1), (5, 1090), (300, 3), (84, 196)])]
     for j, (x, o) in enumerate(zip(xs, t.ops.colsum_group([t.inp(x, f"g{j}") for j, x in enumerate(xs)]))):
         t.out(f"g{j}", o, lambda x=x: x.double().sum(0))
@@ -1345,17 +1586,14 @@ def arena():
 
 @contextlib.contextmanager
 def _placed(ops, arena, mp, skew_out):
-    """ops as the case sees it: torch -> the arena proxy, a fresh workspace cache (dropped again at the end), workspaces
-    and prepared-weight slots carved as scratch, lib() -> the call recorder"""
+    """ops as the case sees it: torch -> the arena proxy, workspaces of exactly the requested size and prepared-weight
+    slots carved as scratch, lib() -> the call recorder"""
     from scat_amd._lib import lib
 
     proxy = _guard.TorchProxy(arena, skew_out)
     rec = _Recorder(lib())
-    real_ws, real_slot = ops.workspace, ops.WeightPrep.slot
-
-    def workspace(nbytes, device, slot="default"):
-        with proxy.scratch():
-            return real_ws(nbytes, device, slot)
+    real_slot = ops.WeightPrep.slot
+    workspace = _guard.exact_workspace(proxy, ops._stream)
 
     def wp_slot(self, *a, **k):
         with proxy.scratch():
@@ -1363,7 +1601,6 @@ def _placed(ops, arena, mp, skew_out):
 
     with mp.context() as m:
         m.setattr(ops, "torch", proxy)
-        m.setattr(ops, "_ws_cache", {})
         m.setattr(ops, "workspace", workspace)
         m.setattr(ops.WeightPrep, "slot", wp_slot)
         m.setattr(ops, "lib", lambda: rec)
@@ -1407,6 +1644,12 @@ def test_guarded_placements(case, math, fill, ops, arena, monkeypatch):
                 if pl == "A":
                     missing = set(case.syms) - rec.called
                     assert not missing, f"{case.name}: never called {sorted(missing)} (called: {sorted(rec.called)})"
+                    for sym in case.syms:
+                        if sym in WS:
+                            seen = sorted(set(rec.ws.get(sym, [])))
+                            print(f"{case.name} [{pl}] {sym}: (ws_bytes, queried) {seen}")
+                            assert any(q > 0 and b == q for b, q in seen), \
+                                f"{case.name}: {sym} never ran with a workspace of exactly its non-zero queried size: {seen}"
                 res = {}
                 for name, got, ref, gate in t.outs:
                     gate = case.gate if gate is None else gate

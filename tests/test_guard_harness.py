@@ -1,6 +1,7 @@
 """The guard arena (tests/_guard.py) proves itself on CPU memory: the mistakes are planted by Python code, nothing on a
-GPU is made to misbehave.  Plus the completeness test: every pointer-taking entry point of include/scat_hip.h is either
-exercised by a case of tests/test_gpu_guard.py or exempted by name with a reason."""
+GPU is made to misbehave.  Plus the completeness tests: every pointer-taking entry point of include/scat_hip.h is either
+exercised by a case of tests/test_gpu_guard.py or exempted by name with a reason, and every entry point that takes a
+workspace has its row in that module's WS table, with shapes at which its query returns the bytes written there."""
 import re
 
 import pytest
@@ -181,6 +182,53 @@ def test_torch_proxy_carves_allocations_out_of_the_arena():
         a.check()
 
 
+# ------------------------------------------------------------------ the exact-size workspace stand-in
+
+def _overshoot(ws, at):
+    """one byte written through ws's own storage at offset ``at`` of it: what a kernel that trusts a larger size does"""
+    torch.as_strided(ws, (at + 1,), (1,))[at] = 0
+
+
+@pytest.mark.parametrize("fill", ["nan", "big"])
+@pytest.mark.parametrize("n", [1, 13, 4608, 61936, 592703])
+def test_a_workspace_request_gets_exactly_its_bytes_and_one_byte_more_is_seen(n, fill):
+    a = Arena("cpu", fill, **SMALL)
+    workspace = _guard.exact_workspace(TorchProxy(a, skew=1))
+    ws = workspace(n, "cpu", "slot")
+    slot = a.slots[-1]
+    assert ws.dtype == torch.uint8 and ws.numel() == n == slot.nbytes and slot.view.data_ptr() == ws.data_ptr()
+    assert ws.data_ptr() % 16 == 0 and slot.name.startswith("scratch") and slot.out and not slot.finite
+    assert a.buf.data_ptr() + slot.off == ws.data_ptr()
+    assert torch.equal(ws, a._pattern(slot.off, n, _guard.GUARD_NAN_BITS)), "a workspace starts as the guard NaN"
+    a.check()
+    _overshoot(ws, n - 1)                    # the last byte it asked for is its own
+    a.check()
+    _overshoot(ws, n)                        # the first byte it did not ask for is not
+    with pytest.raises(GuardError, match=r"guard AFTER 'scratch\d+' damaged: 1 bytes, first at \+0 and last at \+0"):
+        a.check()
+
+
+def test_workspace_requests_are_never_rounded_up_or_shared():
+    a = Arena("cpu", "nan", **SMALL)
+    workspace = _guard.exact_workspace(TorchProxy(a))
+    big, small, again, zero = workspace(9216, "cpu"), workspace(6336, "cpu"), workspace(9216, "cpu"), workspace(0, "cpu", "wt")
+    assert [t.numel() for t in (big, small, again, zero)] == [9216, 6336, 9216, 16]       # (0 bytes: 16, a non-null pointer)
+    assert len({t.data_ptr() for t in (big, small, again, zero)}) == 4 and len(a.slots) == 4
+    assert all(s.nbytes == t.numel() for s, t in zip(a.slots, (big, small, again, zero)))
+    assert all(b - s >= 64 << 10 for s, b, _, _ in a.bands()[1:-1])
+    # a full arena: the same (slot, stream, bytes) is handed out again, nothing else is
+    first = workspace(600 << 10, "cpu", "gg")
+    second = workspace(600 << 10, "cpu", "gg")
+    third = workspace(600 << 10, "cpu", "gg")
+    assert second.data_ptr() != first.data_ptr() and third.data_ptr() == second.data_ptr() and third.numel() == 600 << 10
+    for other in ((600 << 10) - 1, (600 << 10) + 1):
+        with pytest.raises(MemoryError):
+            workspace(other, "cpu", "gg")
+    with pytest.raises(MemoryError):
+        workspace(600 << 10, "cpu", "another slot")
+    a.check()
+
+
 # ------------------------------------------------------------------ completeness of tests/test_gpu_guard.py
 
 EXEMPT_KINDS = ("returns a string", "host-side state only", "diagnostic build only")
@@ -219,3 +267,102 @@ def test_every_case_fixes_its_skew_outcome_and_gate_beforehand():
             assert e == "compute" or re.fullmatch(r"SCAT_E_(SHAPE|ARG|WORKSPACE)", e), (c.name, pl, e)
         if not c.direct:
             assert all(e == "compute" for e in c.expect.values()), f"{c.name}: a dispatching wrapper must compute"
+
+
+# ------------------------------------------------------------------ the workspace table of tests/test_gpu_guard.py
+
+@pytest.fixture(scope="module")
+def L():
+    from scat_amd import build
+    from scat_amd._lib import lib
+
+    build.build(verbose=False)
+    return lib()
+
+
+def _header_protos():
+    from scat_amd._lib import HEADERS, parse_header
+
+    protos = {}
+    for h in HEADERS:
+        protos.update(parse_header(h))
+    return protos
+
+
+def test_every_entry_point_with_a_workspace_has_its_row():
+    import test_gpu_guard as G
+
+    protos = _header_protos()
+    with_ws = [n for n, (_, args) in protos.items() if any(an == "ws_bytes" for _, an in args)]
+    assert len(with_ws) >= 25, "the header parse lost its prototypes"
+    assert all(any(an == "ws" for _, an in protos[n][1]) for n in with_ws)
+    assert list(G.WS) == with_ws, (sorted(set(with_ws) - set(G.WS)), sorted(set(G.WS) - set(with_ws)))
+    cases = {s for c in G.CASES for s in c.syms}
+    for name, row in G.WS.items():
+        assert row.align in (4, 8, 16) and row.short in ("reject", "single_pass"), name
+        assert row.misaligned in ("SCAT_E_WORKSPACE", "SCAT_E_ARG", "single_pass"), name
+        assert (row.short == "single_pass") == (row.misaligned == "single_pass") == (name == "scat_gemm"), name
+        assert row.math in (None, 1) and row.nbytes > 0 and (row.shape2 is None) == (row.nbytes2 is None), name
+        assert (row.shape2 is None) == (row.branch is None), name
+        assert row.where in ("tests/test_cabi.py", "tests/test_eval.py"), name
+        # the rows of include/scat_hip.h run inside the arena with exact workspaces; scat_eval.h has tests/test_gpu_eval.py
+        assert (name in cases) == (row.where == "tests/test_cabi.py"), name
+
+
+def test_every_workspace_query_sizes_a_row():
+    import test_gpu_guard as G
+
+    queries = {n for n in _header_protos() if n.endswith("_ws")}
+    assert len(queries) >= 19
+    used = {row.query for row in G.WS.values() if row.query}
+    used |= {G._wprep_query(dict(kind=k, Cout=1, Cin=1, KH=1, KW=1))[0] for k in range(6)}      # scat_wprep_jobs: by kind
+    assert used == queries, (sorted(queries - used), sorted(used - queries))
+
+
+def _named(G, L, name, shape):
+    return dict(zip([an for _, an in L.protos[name][1]], G.ws_call_args(L, name, shape, 0, 0)))
+
+
+def test_each_rows_shapes_give_the_bytes_written_in_the_table(L):
+    """the byte counts were taken from the host code's own arithmetic; a plan that moves shows here, on the CPU"""
+    import test_gpu_guard as G
+
+    for name, row in G.WS.items():
+        assert G.ws_query(L, name, _named(G, L, name, row.shape)) == row.nbytes > 0, name
+        if row.shape2 is not None:
+            assert G.ws_query(L, name, _named(G, L, name, row.shape2)) == row.nbytes2 != row.nbytes, name
+        if row.unused and set(row.unused) - {"null"}:
+            assert G.ws_query(L, name, _named(G, L, name, dict(row.shape, **row.unused))) == 0, name
+    # the branches the table names, from the formulas of the host code
+    assert G.WS["scat_bn_bwd"].nbytes == 32 * (4 * 32 + 16) and G.WS["scat_bn_bwd"].nbytes2 == 200 * (11 * 32 + 16)
+    assert G.WS["scat_gemm"].nbytes == 3 * 84 * 588 * 4 and G.WS["scat_gemm_group"].nbytes == 2 * (70 * 33 + 3 * 147) * 4
+    assert G.WS["scat_colsum_sliced"].nbytes == 79 * 196 * 4
+    assert G.WS["scat_layernorm_bwd"].nbytes == (40 + 2) * 196 * 4 and G.WS["scat_layernorm_bwd"].nbytes2 == (21400 + 2 * 79) * 196 * 4
+    assert G.WS["scat_conv7x7_s2_wgrad_split"].nbytes == 6 * 64 * 147 * 4            # 22 rows, 4 per workgroup
+    assert G.WS["scat_conv7x7_s2_wgrad_split"].nbytes2 == 618 * 64 * 147 * 4         # 3088 rows, 5 per workgroup
+
+
+class _NoLaunch:
+    """the library's queries, and entry points that do nothing: what the recorder notes is looked at without a launch"""
+
+    def __init__(self, real):
+        self._real, self.protos = real, real.protos
+
+    def __getattr__(self, name):
+        return getattr(self._real, name) if name.endswith("_ws") else (lambda *a: 0)
+
+
+def test_the_recorder_notes_the_workspace_of_every_row(L):
+    import test_gpu_guard as G
+
+    rec = G._Recorder(_NoLaunch(L))
+    for name, row in G.WS.items():
+        for shape, nbytes in ((row.shape, row.nbytes), (row.shape2, row.nbytes2)):
+            if shape is not None:
+                getattr(rec, name)(*G.ws_call_args(L, name, shape, 0x7000000, nbytes + 5))
+    assert rec.called == set(G.WS)
+    for name, row in G.WS.items():
+        want = [(row.nbytes + 5, row.nbytes)] + ([(row.nbytes2 + 5, row.nbytes2)] if row.shape2 is not None else [])
+        assert rec.ws[name] == want, (name, rec.ws[name], want)
+    rec.scat_relu_fwd(16, 32, 4, 0)                                    # (an entry point without a row: only its name)
+    assert "scat_relu_fwd" in rec.called and "scat_relu_fwd" not in rec.ws
