@@ -1,5 +1,6 @@
-"""ctypes binding of libscat_hip.so. Prototypes are parsed from include/scat_hip.h (the train step) and
-include/scat_eval.h (on-device evaluation), so the headers are the single source of truth for the C ABI. The product path has NO fallback: if the
+"""ctypes binding of libscat_hip.so. Prototypes are parsed from include/scat_hip.h (the train step),
+include/scat_eval.h (on-device evaluation) and include/scat_mano.h (the MANO layer), so the headers are the single source
+of truth for the C ABI. The product path has NO fallback: if the
 library is missing, importing a kernel raises."""
 from __future__ import annotations
 
@@ -10,7 +11,8 @@ import re
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "include", "scat_hip.h")
 EVAL_HEADER = os.path.join(HERE, "..", "include", "scat_eval.h")
-HEADERS = (HEADER, EVAL_HEADER)   # every public header of the one library; parse_header() defaults to the first
+MANO_HEADER = os.path.join(HERE, "..", "include", "scat_mano.h")
+HEADERS = (HEADER, EVAL_HEADER, MANO_HEADER)   # every public header of the one library; parse_header() defaults to the first
 LIBPATH = os.path.join(HERE, "libscat_hip.so")
 if os.environ.get("SCAT_LIBPATH"):
     # measurement tools only (tools/pw_stamp.py, rows_stamp.py): the -DSCAT_DIAG build whose kernels can overwrite their
@@ -68,10 +70,11 @@ class _Lib:
         if torch.cuda.is_available():
             torch.cuda.init()
         self.cdll = ctypes.CDLL(LIBPATH)
-        self.protos = {}
-        for h in HEADERS:
-            self.protos.update(parse_header(h))
-        for name, (rt, at) in self.protos.items():
+        # by_header: {header path: its prototypes}, every public header; protos: the train step and evaluation merged, the
+        # table the workspace tests index (tests/test_eval.py pins it to those two headers)
+        self.by_header = {h: parse_header(h) for h in HEADERS}
+        self.protos = {**self.by_header[HEADER], **self.by_header[EVAL_HEADER]}
+        for name, (rt, at) in ((n, p) for protos in self.by_header.values() for n, p in protos.items()):
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = rt
             fn.argtypes = [t for t, _ in at]
