@@ -123,20 +123,6 @@ int scat_planes_from_f32(const float* src, void* planes, int B, int C, int HW, c
 int scat_conv1x1_planes(const void* planes, const float* w, float* dst, int B, int C, int HW, int M, int transposed,
                         const float* bias, int accumulate, void* ws, int64_t ws_bytes, int w_ready, int lds_stages,
                         void* stream);
-/* ---- persistent stream-K schedule for the pointwise kernels ----
- * One tile per workgroup leaves the last round of a launch half empty at batch 96 (588 / 1 176 tiles of 128 x 128 on the
- * 768 workgroup slots of the chip).  scat_streamk_arm(buf, bytes) before a call of scat_conv1x1_s1 / scat_conv1x1_s1_bnb
- * lends its kernel a scratch buffer (scat_streamk_bytes(), 16-B aligned, zero-filled when first handed over, used by one
- * stream at a time): the launch then runs as one persistent grid whose workgroups share the (tile, 32-channel stage)
- * list equally and exchange the partial sums of split tiles through that buffer — deterministic (a tile's partial sums
- * are added in a fixed order that depends on the shape only), same epilogues.  The arming is per host thread and is
- * consumed by the next pointwise call whether or not it qualifies (>= 256 tiles, no taps, split products).
- * scat_streamk_error(buf, bytes, stream) SYNCHRONISES the stream and reports whether a workgroup ever gave up waiting
- * for a partial tile (a diagnostic for tests; the wait is bounded so a fault can not hang the queue).  No reference
- * counterpart: scheduling of nn.Conv2d(k=1), models/resnet.py:65-72. */
-int64_t scat_streamk_bytes(void);
-int scat_streamk_arm(void* buf, int64_t bytes);
-int scat_streamk_error(const void* buf, int64_t bytes, void* stream);
 /* ---- prepared weights (split-operand products) ----
  * The five entry points above that take `w_ready` re-lay their weights into ws (three bf16 planes in MFMA operand
  * order) before their main kernel: one small launch per convolution and direction, 114 per ResNet-50 train step

@@ -13,8 +13,6 @@
 //
 // Replaces nn.Conv2d(k=1) and its input gradient as called at models/resnet.py:65-67,70-72,84-92 of the
 // reference (conv1/conv3 of every Bottleneck) and the 1x1 reductions of models/hand_net.py, fp32.
-#include <atomic>
-
 #include "conv_common.h"
 #include "split.h"
 
@@ -228,12 +226,9 @@ __global__ __launch_bounds__(NT, (BM * BN >= 128 * 128 ? 2 : 3)) void conv1x1_ke
 // about one vector instruction per MFMA (tools/mfma_probe.hip, PROBE_PC=1): every instruction taken out of the staging
 // is time given back to the MFMAs.
 //
-// pw_split_tile: the contraction stages [s_begin, s_end) of one output tile (a whole tile for the one-tile-per-workgroup
-// kernel; a K-segment of it for the persistent stream-K kernel below).  `post(acc)` runs on the finished accumulators
-// and says whether the epilogue (store_tile) follows.
-template <int WM, int BN, bool TF, bool DS, bool STEM, bool PL, class Post, bool BNB = false>
-__device__ __forceinline__ void pw_split_tile(const PwDesc& d, const OutDesc& dc, const int tile, const int s_begin,
-                                              const int s_end, Post post) {
+// pw_split_tile: one output tile, its nstage = ntap * ceil(C / 32) contraction stages and the epilogue (store_tile).
+template <int WM, int BN, bool TF, bool DS, bool STEM, bool PL, bool BNB = false>
+__device__ __forceinline__ void pw_split_tile(const PwDesc& d, const OutDesc& dc, const int tile, const int nstage) {
     static_assert(!(TF && DS), "one input transform at a time");
     static_assert(!(PL && STEM), "the stem has its own staging");
     static_assert(!STEM || (!TF && !DS), "the stem reads the raw image");
@@ -248,8 +243,7 @@ __device__ __forceinline__ void pw_split_tile(const PwDesc& d, const OutDesc& dc
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, lh = lane >> 5;
-    const int nsc = (d.C + PW_KS - 1) / PW_KS;       // 32-channel stages per tap
-    const int nstage = s_end;                          // contraction order: (tap, channel); loads past s_end read zeros
+    const int nsc = (d.C + PW_KS - 1) / PW_KS;       // 32-channel stages per tap; contraction order: (tap, channel)
 
     // ---- activation staging: this thread's pixel, k-octets g0 + r*(NT/BN)
     const __amdgpu_buffer_rsrc_t rsrc_b = make_rsrc(d.src, d.nsrc);
@@ -442,14 +436,14 @@ __device__ __forceinline__ void pw_split_tile(const PwDesc& d, const OutDesc& dc
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0;
     if (stamp) ts0 = __builtin_amdgcn_s_memrealtime();
     if constexpr (DS) {
-        load_b(s_begin, S0{});
-        load_a(areg[0], 2 * s_begin);
-        store_b(s_begin, Bs(0), S0{});
+        load_b(0, S0{});
+        load_a(areg[0], 0);
+        store_b(0, Bs(0), S0{});
         __syncthreads();
         read_b(bfr[0], Bs(0), 0, 0);
-        for (int s = s_begin; s < nstage; ++s) {
-            const u32x4* bcur = Bs((s - s_begin) & 1);
-            u32x4* bnext = Bs((s - s_begin + 1) & 1);
+        for (int s = 0; s < nstage; ++s) {
+            const u32x4* bcur = Bs(s & 1);
+            u32x4* bnext = Bs((s + 1) & 1);
             load_b(s + 1, S0{});
             static_for<2 * NI>([&](auto i_tag) {
                 constexpr int I = decltype(i_tag)::value, t = I / NI, b = I % NI;
@@ -466,10 +460,10 @@ __device__ __forceinline__ void pw_split_tile(const PwDesc& d, const OutDesc& dc
             read_b(bfr[0], bnext, 0, 0);
         }
     } else {
-        load_b(s_begin, S0{});
-        load_b(s_begin + 1, S1{});
-        load_a(areg[0], 2 * s_begin);
-        store_b(s_begin, Bs(0), S0{});
+        load_b(0, S0{});
+        load_b(1, S1{});
+        load_a(areg[0], 0);
+        store_b(0, Bs(0), S0{});
         __syncthreads();
         read_b(bfr[0], Bs(0), 0, 0);
         if (stamp) ts1 = __builtin_amdgcn_s_memrealtime();
@@ -496,13 +490,12 @@ __device__ __forceinline__ void pw_split_tile(const PwDesc& d, const OutDesc& dc
             __syncthreads();
             read_b(bfr[0], bnext, 0, 0);
         };
-        for (int s = s_begin; s < nstage; s += 2) {
+        for (int s = 0; s < nstage; s += 2) {
             stage(s, S0{});
             if (s + 1 < nstage) stage(s + 1, S1{});
         }
     }
     if (stamp) ts2 = __builtin_amdgcn_s_memrealtime();
-    if (!post(acc)) return;
     store_tile<1, NI, BM, BN, WM, WN, BNB>(acc, dc, d.M, d.npix, i0, j0, 0);
     if (stamp) {
         __syncthreads();
@@ -535,117 +528,7 @@ __global__ __launch_bounds__(NT, 3) void conv1x1_split_kernel(PwDesc d, OutDesc 
             while (__builtin_amdgcn_s_memrealtime() - t0 < wait) __builtin_amdgcn_s_sleep(32);
         }
     }
-    auto all = [](auto&) { return true; };
-    pw_split_tile<WM, BN, TF, DS, STEM, PL, decltype(all), BNB>(d, dc, tile, 0, nstage, all);
-}
-
-// ---------------------------------------------------------------- persistent stream-K schedule
-//
-// At batch 96 the tile counts of this network are multiples of 147 (96 * 49 * 2^k / 128): 588 or 1 176 tiles on the
-// 768 workgroup slots of the chip (256 CUs x 3) — the last round of a one-tile-per-workgroup grid is half empty, and
-// in-kernel time stamps (tools/pw_stamp.py) show the stage loop itself already saturates the matrix pipe.  Here the grid
-// IS the slot count: the tiles x stages of a launch are one list of (tile, stage) units, cut into equal contiguous
-// ranges, one per workgroup (Osama et al., "Stream-K", PPoPP'23).  A range is at most: the tail of a tile, whole tiles,
-// the head of a tile.
-//   * XCD-aware: hardware deals workgroup b to XCD b % 8.  Each XCD gets a contiguous chunk of whole tiles (as xcd_remap
-//     does) and its G / 8 workgroups stream over that chunk only, so a split tile's two halves, its weights and its
-//     activation panel stay in one L2.
-//   * A workgroup walks its range from the END: the head segment of its last tile comes first — its accumulators go to
-//     the workgroup's slot of the scratch buffer and a flag is raised — and the tail segment of its first tile comes
-//     last: the workgroup that holds a tile's tail owns the tile, adds the partial sums of its predecessors (in
-//     descending workgroup order: the result depends on the shape only, bit for bit reproducible) and runs the epilogue
-//     (bias / accumulate / BatchNorm sums unchanged: they see the complete accumulators).
-//   * An owner only ever waits for workgroups with a LOWER block index on the same XCD, whose partial was the first
-//     thing they did: hardware dispatches blocks in index order, so the wait can not deadlock whatever else occupies
-//     the GPU, and in practice never spins.  The spin is bounded all the same; exhaustion raises a sticky device-side
-//     error word (scat_device_error) instead of hanging the queue.
-//   * Partials and flags are written and read with agent-coherent (sc1) accesses: correct even if the two workgroups
-//     did not share an L2, and no L2 write-back fence (buffer_wbl2) anywhere.
-struct SkDesc {
-    float* part;          // [G][BM * BN] accumulator images in fragment order
-    uint32_t* flags;      // [G]: == id once the workgroup's partial is complete
-    uint32_t* err;        // sticky error word
-    uint32_t id;          // unique per launch (the scratch buffer is recycled between launches)
-    int G;                // workgroups = slots, multiple of 8
-    int coh;              // 1: partials through agent-coherent (sc1, write-through) accesses; 0: through the XCD's L2
-};
-
-template <int WM, int BN, bool TF, bool DS = false, bool PL = true>
-__global__ __launch_bounds__(NT, 3) void conv1x1_sk_kernel(PwDesc d, OutDesc dc, SkDesc sk) {
-    constexpr int BM = 32 * WM, WN = 4 / WM, NI = BN / (32 * WN);
-    const int mt = (d.M + BM - 1) / BM, nt = (d.npix + BN - 1) / BN;
-    const int T = mt * nt;
-    const int nstage = d.ntap * ((d.C + PW_KS - 1) / PW_KS);
-    const int x = blockIdx.x & 7, s = blockIdx.x >> 3, Gx = sk.G >> 3;
-    const int q = T >> 3, r = T & 7;
-    const int t0 = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;      // this XCD's tiles: [t0, t0 + tcount)
-    const int tcount = q + (x < r ? 1 : 0);
-    const int64_t U = (int64_t)tcount * nstage;
-    auto ubeg = [&](int w) { return (int)((int64_t)w * U / Gx); };      // unit range of workgroup w of this XCD
-    const int u0 = ubeg(s), u1 = ubeg(s + 1);
-    const int tid = threadIdx.x;
-    const __amdgpu_buffer_rsrc_t rp = make_rsrc(sk.part, (int64_t)sk.G * BM * BN);
-    constexpr int SC1 = 16;                                                // agent-coherent cache policy (gfx940+)
-
-    for (int u = u1; u > u0;) {
-        const int tl = (u - 1) / nstage;                                   // local tile of the range's last unit
-        const int ua = tl * nstage;
-        const int a = (u0 > ua ? u0 : ua) - ua, e = u - ua;                // stages [a, e) of that tile
-        u = ua + a;
-        pw_split_tile<WM, BN, TF, DS, false, PL>(d, dc, t0 + tl, a, e, [&](f32x16 (&acc)[1][NI]) {
-            if (a == 0 && e == nstage) return true;                        // a whole tile: nothing to exchange
-            if (e != nstage) {
-                // head (or middle) segment: publish the partial sums
-                const int slot = (x * Gx + s) * (BM * BN * 4);
-#pragma unroll
-                for (int b = 0; b < NI; ++b)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        u32x4 v = {__float_as_uint(acc[0][b][4 * k]), __float_as_uint(acc[0][b][4 * k + 1]),
-                                   __float_as_uint(acc[0][b][4 * k + 2]), __float_as_uint(acc[0][b][4 * k + 3])};
-                        if (sk.coh) __builtin_amdgcn_raw_buffer_store_b128(v, rp, ((b * 4 + k) * NT + tid) * 16, slot, SC1);
-                        else __builtin_amdgcn_raw_buffer_store_b128(v, rp, ((b * 4 + k) * NT + tid) * 16, slot, 0);
-                    }
-                __builtin_amdgcn_s_waitcnt(0);                             // this thread's stores have been acknowledged
-                __syncthreads();                                           // ... every thread's
-                if (tid == 0) __hip_atomic_store(sk.flags + x * Gx + s, sk.id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-            // tail segment: this workgroup owns the tile — add the predecessors' partial sums, nearest first
-            for (int w = s - 1; w >= 0; --w) {
-                if (ubeg(w) == ubeg(w + 1)) continue;                      // an empty range publishes nothing
-                if (tid == 0) {
-                    int spins = 0;
-                    while (__hip_atomic_load(sk.flags + x * Gx + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != sk.id) {
-                        __builtin_amdgcn_s_sleep(8);
-                        if (++spins > (1 << 22)) {                         // seconds: something is badly wrong
-                            __hip_atomic_store(sk.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            break;
-                        }
-                    }
-                }
-                __syncthreads();
-                const int slot = (x * Gx + w) * (BM * BN * 4);
-#pragma unroll
-                for (int b = 0; b < NI; ++b) {
-                    u32x4 v[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        v[k] = sk.coh ? __builtin_amdgcn_raw_buffer_load_b128(rp, ((b * 4 + k) * NT + tid) * 16, slot, SC1)
-                                      : __builtin_amdgcn_raw_buffer_load_b128(rp, ((b * 4 + k) * NT + tid) * 16, slot, 1);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        acc[0][b][4 * k] += __uint_as_float(v[k].x);
-                        acc[0][b][4 * k + 1] += __uint_as_float(v[k].y);
-                        acc[0][b][4 * k + 2] += __uint_as_float(v[k].z);
-                        acc[0][b][4 * k + 3] += __uint_as_float(v[k].w);
-                    }
-                }
-                if (ubeg(w) <= ua) break;                                  // that one started the tile
-            }
-            return true;
-        });
-    }
+    pw_split_tile<WM, BN, TF, DS, STEM, PL, BNB>(d, dc, tile, nstage);
 }
 
 // ---------------------------------------------------------------- producer / consumer wave specialisation
@@ -654,62 +537,29 @@ __global__ __launch_bounds__(NT, 3) void conv1x1_sk_kernel(PwDesc d, OutDesc dc,
 // them into bf16 terms, write LDS, read fragments, issue MFMAs.  Its instruction stream per 32-channel stage is
 // ~230 VALU + ~250 SALU + 24 LDS reads + 22 loads around 48 MFMAs, and a wavefront issues in order: the matrix pipe
 // idles while its owner splits (PMC: 0.34 busy at 2.3 wavefronts per SIMD, half of every wavefront's life spent
-// waiting to issue).  Here a 512-thread workgroup has two kinds of wavefront:
-//   * wavefronts 4-7, producers: global loads (three stages ahead) -> fused BatchNorm+ReLU -> three-way split ->
+// waiting to issue).  Here a 768-thread workgroup has two kinds of wavefront:
+//   * wavefronts 8-11, producers: global loads (three stages ahead) -> fused BatchNorm+ReLU -> three-way split ->
 //     LDS (two stages ahead of the readers, three buffers).  No MFMA, no LDS reads.
-//   * wavefronts 0-3, consumers: weights straight from L2 into operand registers (pre-split planes), activation
-//     fragments from LDS, MFMAs.  No staging VALU; the first fragment of the next stage is read before the barrier
-//     because that stage was published a barrier earlier.
-// One s_barrier per stage joins the two streams.  A SIMD holds one consumer and one producer per workgroup, two
-// workgroups per CU at MI = 1: the matrix pipe of a SIMD is fed by two wavefronts whose streams are MFMA + LDS
-// reads only, the VALU by two whose streams never wait for the matrix pipe.
-// DIAG (timing experiments only, results are wrong): 1 = no activation loads, 2 = no weight loads, 4 = no MFMAs,
-// 8 = no output stores, 16 = no split / LDS writes
+//   * wavefronts 0-7, consumers (32 rows each): weights straight from L2 into operand registers (pre-split planes),
+//     activation fragments from LDS, 32x32x16 MFMAs.  No staging VALU; the first fragment of the next stage is read
+//     before the barrier because that stage was published a barrier earlier.
+// One s_barrier per stage joins the two streams.  A 256 x 128 tile is staged once for eight consumers: a SIMD holds two
+// consumers and one producer of ONE workgroup per CU, its matrix pipe fed by two wavefronts whose streams are MFMA +
+// LDS reads only, its VALU by one whose stream never waits for the matrix pipe.
 // W4 (pointwise stride-1 layers with HW % 4 == 0): column (b, c) of the tile is pixel 4c + b instead of 32b + c.  A
 // producer lane then owns FOUR CONSECUTIVE pixels of four channels — four 16-byte loads per stage instead of sixteen
 // 4-byte ones, LDS writes of 8 bytes that consecutive lanes place in consecutive slots — and a consumer lane's four
 // accumulator columns are four consecutive pixels of one row: the epilogue stores 16 bytes per instruction instead of
 // 4.  The MFMA does not care which pixel a column is; only the two ends of the kernel know.
-// NCW consumer wavefronts (32 MI rows each) + 4 producers.  NCW = 8: a 256 x 128 tile staged once for twice the rows —
-// half the activation traffic and producer work per MFMA, two consumers per SIMD inside ONE workgroup per CU.
-// S16: the consumers issue v_mfma_f32_16x16x32_bf16 (a whole 32-channel stage per instruction, 16 x 16 tiles) instead of
-// 32x32x16: the same fragments, planes and LDS image, addressed as lane (l & 15, k-octet l >> 4); the chip holds a
-// higher clock on this shape (tools/mfma_probe.hip: +5 % with the LDS reads).
-// RING = R > 0: no workgroup barrier in the main loop.  The stage buffers form a ring of R slots with two LDS words per
-// slot: FULL (each of the 4 producer wavefronts adds 1 once its part of the stage is written) and FREE (each of the NCW
-// consumers adds 1 once it has read the stage).  A producer runs ahead until the ring is full, a consumer waits only for
-// data that is not there: the two streams are coupled by data, not by a rendezvous every stage (with a barrier per
-// stage, a late load stalls the MFMA wavefronts even when the fragments they need next are already in LDS).  Spins are
-// bounded (the kernel ends with wrong results rather than hanging should a count be wrong).
-template <int MI, bool TF, int DIAG = 0, bool W4 = false, int NCW = 4, bool S16 = false, int RING = 0>
-__global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2))) void conv1x1_pc_kernel(PwDesc d, OutDesc dc) {
-    constexpr int BN = 128, BM = 32 * NCW * MI, NI = 4, PT = 256;
-    static_assert(RING == 0 || (!W4 && !S16 && RING >= 3), "ring form: plain columns, 32x32x16");
+// (Four consumers, 64 rows per consumer, 16x16x32 consumers and a barrier-free ring were measured and lost: DESIGN 1b.)
+constexpr int PC_NCW = 8;                             // consumer wavefronts; + 4 producers
+template <bool TF, bool W4>
+__global__ __launch_bounds__((PC_NCW + 4) * 64, 3) void conv1x1_pc_kernel(PwDesc d, OutDesc dc) {
+    constexpr int NCW = PC_NCW, BN = 128, BM = 32 * NCW, NI = 4, PT = 256;
     constexpr int NIT = 4 * BN / PT;                  // k-octets per producer thread per 32-channel stage
     constexpr int BUF = 12 * BN;                      // u32x4 per buffer: [3 planes][4 k-octets][BN]
     extern __shared__ __align__(16) float lds[];
     u32x4* const B0 = (u32x4*)lds;
-    // ring form: FULL[R] | FREE[R] behind the R stage buffers
-    unsigned* const ring_full = (unsigned*)(B0 + (RING > 0 ? RING : 3) * BUF);
-    unsigned* const ring_free = ring_full + (RING > 0 ? RING : 0);
-    if constexpr (RING > 0) {
-        if (threadIdx.x < 2 * RING) ring_full[threadIdx.x] = 0u;
-        __syncthreads();
-    }
-    // (relaxed LDS accesses + compiler barriers: the LDS serves one wavefront's requests in order, so "writes, then
-    // lgkmcnt(0), then the count" and "poll, then reads" need no hardware fence; a release/acquire pair would make hipcc
-    // drain vmcnt too and with it the producers' prefetched global loads)
-    auto wait_ge = [&](unsigned* p, unsigned target) {
-        for (int it = 0; it < (1 << 16); ++it) {
-            if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= target) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        asm volatile("" ::: "memory");
-    };
-    auto signal = [&](unsigned* p) {
-        asm volatile("" ::: "memory");
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
 
     const int mt = (d.M + BM - 1) / BM, nt = (d.npix + BN - 1) / BN;
     const int tile = xcd_remap(blockIdx.x, mt * nt);
@@ -746,10 +596,8 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2)))
             const int c0 = st * PW_KS;
             const int vo = (c0 + 8 * g < d.C && st < nstage) ? boff : OOB;      // C % 16 == 0: whole octets
 #pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                if constexpr (DIAG & 1) bst[Q][m] = u32x4{(uint32_t)vo, 0x3f800000u, (uint32_t)m, 0x40000000u};
-                else bst[Q][m] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, vo, (c0 + m) * chw4, 0);
-            }
+            for (int m = 0; m < 4; ++m)
+                bst[Q][m] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, vo, (c0 + m) * chw4, 0);
             if constexpr (TF) {
                 const int co = (c0 + 8 * g + 4 * h < d.C && st < nstage) ? (c0 + 8 * g + 4 * h) * 4 : OOB;
                 tsc[Q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_sc, co, 0, 0));
@@ -772,17 +620,13 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2)))
                     }
                     x[m] = t;
                 }
-                if constexpr (DIAG & 16) {
-                    asm volatile("" ::"v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]));
-                } else {
-                    uint32_t h0, m0, l0, h1, m1, l1;
-                    split3(x[0], x[1], h0, m0, l0);
-                    split3(x[2], x[3], h1, m1, l1);
-                    u32x2* q = base + (size_t)k * 32 * 2;              // position k*32 + p
-                    q[0] = u32x2{h0, h1};
-                    q[(size_t)4 * BN * 2] = u32x2{m0, m1};
-                    q[(size_t)8 * BN * 2] = u32x2{l0, l1};
-                }
+                uint32_t h0, m0, l0, h1, m1, l1;
+                split3(x[0], x[1], h0, m0, l0);
+                split3(x[2], x[3], h1, m1, l1);
+                u32x2* q = base + (size_t)k * 32 * 2;                  // position k*32 + p
+                q[0] = u32x2{h0, h1};
+                q[(size_t)4 * BN * 2] = u32x2{m0, m1};
+                q[(size_t)8 * BN * 2] = u32x2{l0, l1};
             }
         };
         load_b(0, S0{});
@@ -843,25 +687,15 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2)))
                 const int cu = c0 + 8 * (g0u + r * (PT / BN));          // wave-uniform; C % 16 == 0: whole octets
                 const int vo = cu < d.C ? vbase : OOB;
 #pragma unroll
-                for (int m = 0; m < 8; ++m) {
-                    if constexpr (DIAG & 1) bst[Q][r][m] = __int_as_float(vo + m);
-                    else
+                for (int m = 0; m < 8; ++m)
                     bst[Q][r][m] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
                         rsrc_b, vo, (c0 + 8 * r * (PT / BN) + m) * chw4, 0));
-                }
             }
         };
         auto store_b = [&](int st, u32x4* dst, auto set_tag) {
             constexpr int Q = decltype(set_tag)::value;
             const int tap = st / nsc, c0 = (st - tap * nsc) * PW_KS;
             const bool live = (pmask >> (tap < 9 ? tap : 9)) & 1u;       // padding must stay zero AFTER the transform
-            if constexpr (DIAG & 16) {
-#pragma unroll
-                for (int r = 0; r < NIT; ++r)
-#pragma unroll
-                    for (int m = 0; m < 8; ++m) asm volatile("" ::"v"(bst[Q][r][m]));
-                return;
-            }
 #pragma unroll
             for (int r = 0; r < NIT; ++r) {
                 float x[8];
@@ -885,24 +719,6 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2)))
                 dst[(2 * 4 + g) * BN + pcol] = lo;
             }
         };
-        if constexpr (RING > 0) {
-            load_b(0, S0{});
-            load_b(1, S1{});
-            int slot = 0, use = 0;
-            auto put = [&](int ps, auto par_tag) {
-                if (use > 0) wait_ge(ring_free + slot, (unsigned)(NCW * use));     // every consumer has read its last use
-                store_b(ps, B0 + slot * BUF, par_tag);
-                load_b(ps + 2, par_tag);                                           // (the set is free again)
-                __builtin_amdgcn_s_waitcnt(0xc07f);                                // lgkmcnt(0): the writes have landed
-                signal(ring_full + slot);
-                if (++slot == RING) { slot = 0; ++use; }
-            };
-            for (int ps = 0; ps < nstage; ps += 2) {
-                put(ps, S0{});
-                if (ps + 1 < nstage) put(ps + 1, S1{});
-            }
-            return;
-        }
         load_b(0, S0{});
         load_b(1, S1{});
         store_b(0, B0, S0{});
@@ -924,180 +740,58 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2)))
         return;
     }
 
-    if constexpr (S16) {
-        // ------------------------------------------------------------ consumer, 16x16x32 form (MI = 1, plain columns)
-        typedef float f32x4v __attribute__((ext_vector_type(4)));
-        const int l15 = lane & 15, kq = lane >> 4;
-        const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(d.w, d.nw);
-        const int aplane = d.M * 32;
-        const int nchunk = (d.C + 15) / 16;
-        int aoff[2];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-            const int row = i0 + wave * 32 + rb * 16 + l15;
-            aoff[rb] = row < d.M ? row * 32 + (kq & 1) * 16 + (kq >> 1) * 3 * aplane : OOB;
-        }
-        auto load_a = [&](u32x4 (&dst)[3], int st, int rb) {     // the 16 rows rb of stage st: 32 channels per lane group
-            const int tap = st / nsc, ch = (st - tap * nsc) * 2;
-            const bool ok = st < nstage && ch + (kq >> 1) < nchunk;
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-                dst[p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, ok ? aoff[rb] : OOB,
-                                                               ((tap * nchunk + ch) * 3 + p) * aplane, 0);
-        };
-        f32x4v acc[2][8];
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 8; ++cb) acc[rb][cb] = f32x4v{0.f, 0.f, 0.f, 0.f};
-        const int b_frag = kq * BN + l15;
-        auto read_b = [&](u32x4 (&dst)[3], const u32x4* buf, int cb) {
-            const u32x4* p = buf + b_frag + cb * 16;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) dst[q] = p[q * 4 * BN];
-        };
-        auto mfma6 = [&](const u32x4 (&a)[3], const u32x4 (&b)[3], f32x4v c) {
-            const bf16x8 ah = __builtin_bit_cast(bf16x8, a[0]), am = __builtin_bit_cast(bf16x8, a[1]),
-                         al = __builtin_bit_cast(bf16x8, a[2]);
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, b[0]), bm = __builtin_bit_cast(bf16x8, b[1]),
-                         bl = __builtin_bit_cast(bf16x8, b[2]);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, c, 0, 0, 0);
-            return c;
-        };
-        // the two 16-row halves of a stage run one after the other (fragments re-read per half: 48 reads per stage),
-        // so a half's weights are dead after its 8 column blocks and the next stage's load over them has half a stage
-        // of cover: one register set per half
-        u32x4 areg[2][3];
-        u32x4 bfr[2][3];
-        load_a(areg[0], 0, 0);
-        load_a(areg[1], 0, 1);
-        __syncthreads();
-        read_b(bfr[0], B0, 0);
-        int rb_ = 0;
-        for (int s = 0; s < nstage; ++s) {
-            const u32x4* bcur = B0 + rb_ * BUF;
-            rb_ = rb_ == 2 ? 0 : rb_ + 1;
-            const u32x4* bnxt = B0 + rb_ * BUF;
-            static_for<16>([&](auto i_tag) {
-                constexpr int I = decltype(i_tag)::value, rb = I / 8, cb = I % 8;
-                constexpr int fcur = I & 1, fnxt = fcur ^ 1;
-                if constexpr (I == 8) load_a(areg[0], s + 1, 0);       // half 0 is done with its weights
-                if constexpr (I < 15) read_b(bfr[fnxt], bcur, (I + 1) % 8);
-                else read_b(bfr[fnxt], bnxt, 0);                        // published one barrier ago
-                __builtin_amdgcn_sched_barrier(0);
-                acc[rb][cb] = mfma6(areg[rb], bfr[fcur], acc[rb][cb]);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-            load_a(areg[1], s + 1, 1);
-            __syncthreads();
-        }
-        // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-        const __amdgpu_buffer_rsrc_t rc = make_rsrc(dc.p, dc.n);
-        const bool biasi = dc.bias && dc.bias_mode == 1;
-#pragma unroll
-        for (int cb = 0; cb < 8; ++cb) {
-            const int j = j0 + cb * 16 + l15;
-            const bool colok = j < d.npix;
-            const uint32_t jj = colok ? (uint32_t)j : 0u;
-            const uint32_t n = dc.dHW.div(jj);
-            const int coloff = (int)n * dc.C * dc.HW + (int)(jj - n * (uint32_t)dc.HW);
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int i = i0 + wave * 32 + rb * 16 + kq * 4 + r;
-                    const int vo = (colok && i < d.M) ? (coloff + i * dc.HW) * 4 : OOB;
-                    float v = acc[rb][cb][r] + (biasi ? dc.bias[i < d.M ? i : 0] : 0.f);
-                    if (dc.accumulate) v += bload(rc, vo);
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rc, vo, 0, 0);
-                }
-        }
-        return;
-    }
-    // ---------------------------------------------------------------- consumer: rows i0 + wave*32*MI ..
+    // ---------------------------------------------------------------- consumer: rows i0 + wave*32 ..
     const int l31 = lane & 31, lh = lane >> 5;
     const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(d.w, d.nw);
-    int aoff[MI];
+    // (a one-trip loop, left from the form with several row blocks per consumer: without it hipcc orders the address
+    // arithmetic of the wide form differently, and the kernel keeps the instruction stream it was measured with)
+    int aoff = OOB;
 #pragma unroll
-    for (int a = 0; a < MI; ++a) {
-        const int row = i0 + (wave * MI + a) * 32 + l31;
-        aoff[a] = row < d.M ? row * 32 + lh * 16 : OOB;
+    for (int a = 0; a < 1; ++a) {
+        const int row = i0 + (wave + a) * 32 + l31;
+        aoff = row < d.M ? row * 32 + lh * 16 : OOB;
     }
     const int aplane = d.M * 32;
     const int nchunk = (d.C + 15) / 16;
-    auto load_a = [&](u32x4 (&dst)[MI][3], int q) {
+    auto load_a = [&](u32x4 (&dst)[3], int q) {
         const int st = q >> 1, tap = st / nsc, ch = (st - tap * nsc) * 2 + (q & 1);
         const bool ok = ch < nchunk && st < nstage;
 #pragma unroll
-        for (int a = 0; a < MI; ++a)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                if constexpr (DIAG & 2) { dst[a][p] = u32x4{(uint32_t)q, 0x3f803f80u, (uint32_t)aoff[a], 0x3f803f80u}; }
-                else
-                dst[a][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, ok ? aoff[a] : OOB,
-                                                                  ((tap * nchunk + ch) * 3 + p) * aplane, 0);
-            }
+        for (int p = 0; p < 3; ++p)
+            dst[p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, ok ? aoff : OOB, ((tap * nchunk + ch) * 3 + p) * aplane, 0);
     };
-    f32x16 acc[MI][NI];
+    f32x16 acc[1][NI];
 #pragma unroll
-    for (int a = 0; a < MI; ++a)
+    for (int b = 0; b < NI; ++b)
 #pragma unroll
-        for (int b = 0; b < NI; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[0][b][r] = 0.f;
     const int b_frag = lh * BN + l31;
     auto read_b = [&](u32x4 (&dst)[3], const u32x4* buf, int t, int b) {
         const u32x4* p = buf + 2 * t * BN + b_frag + b * 32;
 #pragma unroll
         for (int q = 0; q < 3; ++q) dst[q] = p[q * 4 * BN];
     };
-    u32x4 areg[2][MI][3];
+    u32x4 areg[2][3];
     u32x4 bfr[2][3];
     load_a(areg[0], 0);
-    if constexpr (RING > 0) wait_ge(ring_full, 4u);
-    else __syncthreads();
+    __syncthreads();
     read_b(bfr[0], B0, 0, 0);
-    int rb = 0, ruse = 0;
-    constexpr int NSLOT = RING > 0 ? RING : 3;
+    int rb = 0;
     for (int s = 0; s < nstage; ++s) {
         const u32x4* bcur = B0 + rb * BUF;
-        unsigned* const fcur_free = ring_free + rb;
-        if (++rb == NSLOT) { rb = 0; ++ruse; }
-        const u32x4* bnxt = B0 + rb * BUF;
+        if (++rb == 3) rb = 0;
         static_for<2 * NI>([&](auto i_tag) {
             constexpr int I = decltype(i_tag)::value, t = I / NI, b = I % NI;
             if constexpr (b == 0) load_a(areg[t ^ 1], 2 * s + t + 1);
             constexpr int fcur = I & 1, fnxt = fcur ^ 1;
-            if constexpr (RING > 0 && I == 2 * NI - 1) {
-                if (s + 1 < nstage) wait_ge(ring_full + rb, 4u * (unsigned)(ruse + 1));      // the next stage is in LDS
-            }
             if constexpr (b + 1 < NI) read_b(bfr[fnxt], bcur, t, b + 1);
             else if constexpr (t == 0) read_b(bfr[fnxt], bcur, 1, 0);
-            else read_b(bfr[fnxt], bnxt, 0, 0);          // published one barrier ago
+            else read_b(bfr[fnxt], B0 + rb * BUF, 0, 0);      // the next stage: published one barrier ago
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int a = 0; a < MI; ++a) {
-                if constexpr (DIAG & 4) {
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        asm volatile("" ::"v"(areg[t][a][p]));
-                        asm volatile("" ::"v"(bfr[fcur][p]));
-                    }
-                } else
-                acc[a][b] = mfma_split(areg[t][a], bfr[fcur], acc[a][b]);
-            }
+            acc[0][b] = mfma_split(areg[t], bfr[fcur], acc[0][b]);
             __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr (RING > 0) signal(fcur_free);       // (LDS serves a wavefront's requests in order: its reads of
-        else __syncthreads();                             //  this slot are behind it)
-    }
-    if constexpr (DIAG & 8) {
-        if (d.variant != 0x7fffffff) return;          // (never true: keeps the accumulators live)
+        __syncthreads();
     }
     if constexpr (W4) {
         // lane (l31, lh): rows (reg & 3) + 8 (reg >> 2) + 4 lh of its 32-row block, pixels j0 + 4 l31 .. + 3 = the four
@@ -1110,20 +804,18 @@ __global__ __launch_bounds__((NCW + 4) * 64, (NCW == 8 ? 3 : (MI == 1 ? 4 : 2)))
         const int coloff = (int)n * dc.C * dc.HW + (int)(jj - n * (uint32_t)dc.HW);
         const bool biasi = dc.bias && dc.bias_mode == 1;
 #pragma unroll
-        for (int a = 0; a < MI; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = i0 + (wave * MI + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const bool ok = colok && i < d.M;
-                const int vo = ok ? (coloff + i * dc.HW) * 4 : OOB;
-                const float bi = biasi ? dc.bias[i < d.M ? i : 0] : 0.f;
-                f32x4 v = f32x4{acc[a][0][r] + bi, acc[a][1][r] + bi, acc[a][2][r] + bi, acc[a][3][r] + bi};
-                if (dc.accumulate) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rc, vo, 0, 0));
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rc, vo, 0, 0);
-            }
+        for (int r = 0; r < 16; ++r) {
+            const int i = i0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const bool ok = colok && i < d.M;
+            const int vo = ok ? (coloff + i * dc.HW) * 4 : OOB;
+            const float bi = biasi ? dc.bias[i < d.M ? i : 0] : 0.f;
+            f32x4 v = f32x4{acc[0][0][r] + bi, acc[0][1][r] + bi, acc[0][2][r] + bi, acc[0][3][r] + bi};
+            if (dc.accumulate) v += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rc, vo, 0, 0));
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rc, vo, 0, 0);
+        }
         return;
     }
-    store_tile<MI, NI, BM, BN, NCW, 1>(acc, dc, d.M, d.npix, i0, j0, 0);
+    store_tile<1, NI, BM, BN, NCW, 1>(acc, dc, d.M, d.npix, i0, j0, 0);
 }
 
 // ws[tap][ch][plane][i][16 bf16]: the three bf16 terms of element (i, c, tap).  w is the conv weight
@@ -1210,32 +902,6 @@ static int pw_plain_mode() {
     return m;
 }
 
-// stream-K scratch armed by the caller for the next pointwise launch of this host thread (scat_streamk_arm)
-struct SkScratch { void* buf; int64_t bytes; };
-static thread_local SkScratch g_sk = {nullptr, 0};
-constexpr int SK_G = 768;                             // 256 CUs x 3 workgroups (48 KB of LDS, <= 170 VGPRs each)
-constexpr int64_t SK_PART = (int64_t)SK_G * 128 * 128 * 4;
-constexpr int64_t SK_BYTES = SK_PART + SK_G * 4 + 64;
-static std::atomic<uint32_t> g_sk_id{1};
-static int sk_mode() { return 1; }      // (the caller decides by arming a scratch buffer or not: ops.STREAMK)
-struct SkDisarm { ~SkDisarm() { g_sk.buf = nullptr; g_sk.bytes = 0; } };
-static bool sk_take(SkDesc& sk) {
-    void* b = g_sk.buf;
-    const int64_t n = g_sk.bytes;
-    g_sk.buf = nullptr;
-    g_sk.bytes = 0;
-    if (!b || n < SK_BYTES || ((uintptr_t)b & 15)) return false;
-    sk.part = (float*)b;
-    sk.flags = (uint32_t*)((char*)b + SK_PART);
-    sk.err = sk.flags + SK_G;
-    sk.id = g_sk_id.fetch_add(1, std::memory_order_relaxed);
-    if (sk.id == 0) sk.id = g_sk_id.fetch_add(1, std::memory_order_relaxed);   // 0 is what a fresh buffer holds
-    sk.G = SK_G;
-    static const int coh = diag_env_int("SCAT_SK_COH", 1);
-    sk.coh = coh;
-    return true;
-}
-
 template <int WM, int BN, bool TF, bool DS = false, bool STEM = false>
 static void launch_pw_split(const PwDesc& d, const OutDesc& dc_in, hipStream_t st) {
     constexpr int BM = 32 * WM;
@@ -1261,15 +927,6 @@ static void launch_pw_split(const PwDesc& d, const OutDesc& dc_in, hipStream_t s
             return;
         }
     }
-    if constexpr (!STEM && BN == 128) {
-        // persistent stream-K grid when the caller armed a scratch buffer and the launch has enough tiles to share out
-        SkDesc sk{};
-        if (d.ntap == 1 && d.C % 32 == 0 && pw_plain_mode() && sk_mode() && (int64_t)mt * nt >= 256 && sk_take(sk)) {
-            hipLaunchKernelGGL((conv1x1_sk_kernel<WM, BN, TF, DS>), dim3(SK_G), dim3(NT), lds_bytes, st, d, dc, sk);
-            append_kernel_label("_sk");
-            return;
-        }
-    }
     if constexpr (!STEM) {
         if (d.ntap == 1 && d.C % 32 == 0 && pw_plain_mode()) {
             hipLaunchKernelGGL((conv1x1_split_kernel<WM, BN, TF, DS, false, true>), dim3(mt * nt), dim3(NT), lds_bytes, st,
@@ -1278,6 +935,42 @@ static void launch_pw_split(const PwDesc& d, const OutDesc& dc_in, hipStream_t s
         }
     }
     hipLaunchKernelGGL((conv1x1_split_kernel<WM, BN, TF, DS, STEM>), dim3(mt * nt), dim3(NT), lds_bytes, st, d, dc);
+}
+
+// Tile of the split kernel by cfg: 0 = 128x128, 1 = 64x128, 2 = 64x64 (rows x pixels).  The dual-source and the stem
+// kernels exist on the two 128-pixel tiles and without the fused transform only (their callers ask for nothing else).
+static const char* pw_tile_name(int cfg) {
+    static const char* const names[] = {"128x128", "64x128", "64x64"};
+    return names[cfg];
+}
+
+template <bool DS = false, bool STEM = false>
+static void launch_pw_split_cfg(int cfg, bool tf, const PwDesc& d, const OutDesc& dc, hipStream_t st) {
+    if constexpr (!DS && !STEM) {
+        if (tf) {
+            if (cfg == 0) launch_pw_split<4, 128, true>(d, dc, st);
+            else if (cfg == 1) launch_pw_split<2, 128, true>(d, dc, st);
+            else launch_pw_split<2, 64, true>(d, dc, st);
+            return;
+        }
+        if (cfg == 2) {
+            launch_pw_split<2, 64, false>(d, dc, st);
+            return;
+        }
+    }
+    if (cfg == 0) launch_pw_split<4, 128, false, DS, STEM>(d, dc, st);
+    else launch_pw_split<2, 128, false, DS, STEM>(d, dc, st);
+}
+
+// Geometry of a pointwise problem (one tap, stride 1): B images of C channels x HW pixels, M output rows.
+static PwDesc pw_desc(int B, int C, int HW, int M) {
+    PwDesc d{};
+    d.C = C; d.M = M; d.HW = HW; d.npix = B * HW; d.dHW = FastDiv::make(HW);
+    d.ntap = 1; d.KWt = 1; d.a = 1; d.tb = 1; d.c0y = 0; d.c0x = 0; d.H = 1; d.W = HW; d.OW = HW; d.OHW = HW;
+    d.dOHW = FastDiv::make(HW); d.dOW = FastDiv::make(HW);
+    d.nsrc = (int64_t)B * C * HW;
+    d.variant = tuning();
+    return d;
 }
 
 // ws[chunk = o / 2][plane][co][16 bf16], k16 = 8 (o & 1) + kw: the three bf16 terms of w[co][c][kh][kw], o = 3 kh + c;
@@ -1299,24 +992,23 @@ __global__ __launch_bounds__(256) void stem_wprep_kernel(const float* __restrict
 }
 
 // SCAT_PC: unset = per-layer choice (see scat_conv1x1_s1), 0 = every wavefront stages and multiplies
-// (conv1x1_split_kernel), 5 / 6 = eight consumer wavefronts on a 256 x 128 tile (plain / wide form), 1 = producer/consumer wavefronts with
-// 128-row tiles, 2 = 256-row tiles where the layer has them, 3 / 4 = the same with the wide (pixel-quad) form where the
-// plane allows it
+// (conv1x1_split_kernel), 5 / 6 = eight consumer wavefronts on a 256 x 128 tile (plain / wide form where the plane
+// allows it); any other value = 0
 static int pc_mode() {
     static const int m = [] { const char* e = getenv("SCAT_PC"); return e ? atoi(e) : -1; }();
     return m;
 }
 
-template <int MI, bool TF, int DIAG = 0, bool W4 = false, int NCW = 4, bool S16 = false, int RING = 0>
+template <bool TF, bool W4>
 static void launch_pw_pc(const PwDesc& d, const OutDesc& dc, hipStream_t st) {
-    constexpr int BM = 32 * NCW * MI, BN = 128;
+    constexpr int BM = 32 * PC_NCW, BN = 128;
     const int mt = cdiv(d.M, BM), nt = cdiv(d.npix, BN);
-    constexpr size_t lds_bytes = (size_t)(RING > 0 ? RING : 3) * 12 * BN * 16 + (RING > 0 ? 64 : 0);
-    auto kern = conv1x1_pc_kernel<MI, TF, DIAG, W4, NCW, S16, RING>;
+    constexpr size_t lds_bytes = (size_t)3 * 12 * BN * 16;
+    auto kern = conv1x1_pc_kernel<TF, W4>;
     static bool once = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                             (int)lds_bytes) == hipSuccess);
     (void)once;
-    hipLaunchKernelGGL(kern, dim3(mt * nt), dim3((NCW + 4) * 64), lds_bytes, st, d, dc);
+    hipLaunchKernelGGL(kern, dim3(mt * nt), dim3((PC_NCW + 4) * 64), lds_bytes, st, d, dc);
 }
 
 template <int BM, int BN, bool V4, bool TF>
@@ -1357,17 +1049,8 @@ void taps_split_launch(const TapsGeom& g, const float* src, const float* w, cons
     int cfg = M > 64 ? 0 : 1;
     if ((int64_t)cdiv(M, 128) * cdiv(d.npix, 128) < 256 && (int64_t)cdiv(M, 64) * cdiv(d.npix, 64) >= 256) cfg = 2;
     if (tuning() >= 1 && tuning() <= 3) cfg = tuning() - 1;
-    static const char* const names[] = {"128x128", "64x128", "64x64"};
-    set_kernel_label("%s_split_%sx32%s", label, names[cfg], in_scale ? "_tf" : "");
-    if (in_scale) {
-        if (cfg == 0) launch_pw_split<4, 128, true>(d, dc, st);
-        else if (cfg == 1) launch_pw_split<2, 128, true>(d, dc, st);
-        else launch_pw_split<2, 64, true>(d, dc, st);
-    } else {
-        if (cfg == 0) launch_pw_split<4, 128, false>(d, dc, st);
-        else if (cfg == 1) launch_pw_split<2, 128, false>(d, dc, st);
-        else launch_pw_split<2, 64, false>(d, dc, st);
-    }
+    set_kernel_label("%s_split_%sx32%s", label, pw_tile_name(cfg), in_scale ? "_tf" : "");
+    launch_pw_split_cfg(cfg, in_scale != nullptr, d, dc, st);
 }
 
 }  // namespace scat
@@ -1433,9 +1116,9 @@ extern "C" int scat_conv7x7_s2_fwd_split(const float* x, const float* w, float* 
     OutDesc dc{};
     dc.p = y; dc.mode = 1; dc.I = Cout; dc.J = d.npix; dc.C = Cout; dc.HW = OH * OW; dc.dHW = FastDiv::make(OH * OW);
     dc.n = (int64_t)B * Cout * OH * OW;
-    set_kernel_label("conv7x7_s2_split_%dx128x32", Cout > 64 ? 128 : 64);
-    if (Cout > 64) launch_pw_split<4, 128, false, false, true>(d, dc, st);
-    else launch_pw_split<2, 128, false, false, true>(d, dc, st);
+    const int cfg = Cout > 64 ? 0 : 1;
+    set_kernel_label("conv7x7_s2_split_%sx32", pw_tile_name(cfg));
+    launch_pw_split_cfg<false, true>(cfg, false, d, dc, st);
     SCAT_LAUNCH_CHECK("scat_conv7x7_s2_fwd_split");
     return SCAT_OK;
 }
@@ -1447,7 +1130,6 @@ extern "C" int scat_conv7x7_s2_fwd_split(const float* x, const float* w, float* 
 extern "C" int scat_conv1x1_s1_bnb(const float* g, const float* z, const float* coef3, const float* w, float* dx, int B,
                                    int Cin, int HW, int Cout, int accumulate, void* ws, int64_t ws_bytes,
                                    int w_ready, void* stream) {
-    SkDisarm sk_guard;
     SCAT_REQUIRE(g && z && coef3 && w && dx, SCAT_E_ARG, "scat_conv1x1_s1_bnb: null pointer");
     SCAT_REQUIRE(math_mode() == 1, SCAT_E_ARG, "scat_conv1x1_s1_bnb: needs the split-operand product mode");
     SCAT_REQUIRE(B > 0 && Cin > 0 && HW > 0 && Cout > 0 && Cout % 16 == 0, SCAT_E_SHAPE,
@@ -1458,14 +1140,9 @@ extern "C" int scat_conv1x1_s1_bnb(const float* g, const float* z, const float* 
                  "scat_conv1x1_s1_bnb: tensor exceeds 32-bit byte offsets");
     hipStream_t st = (hipStream_t)stream;
     const int C = Cout, M = Cin;
-    PwDesc d{};
+    PwDesc d = pw_desc(B, C, HW, M);
     d.src = g; d.src2 = z; d.coef = coef3;
-    d.C = C; d.M = M; d.HW = HW; d.npix = B * HW; d.dHW = FastDiv::make(HW);
-    d.ntap = 1; d.KWt = 1; d.a = 1; d.tb = 1; d.c0y = 0; d.c0x = 0; d.H = 1; d.W = HW; d.OW = HW; d.OHW = HW;
-    d.dOHW = FastDiv::make(HW); d.dOW = FastDiv::make(HW);
-    d.nsrc = (int64_t)B * C * HW; d.variant = tuning();
     const int64_t nel = (int64_t)M * ((C + 15) / 16 * 16);
-    const int rblocks = (int)((nel + 255) / 256 < 2048 ? (nel + 255) / 256 : 2048);
     if (!w_ready) wprep_launch(wprep_job(w, ws, M, C, 1, 1, 1, 1, 1, 0, 0, 1), st);
     d.w = (const float*)ws;
     d.nw = (nel * 6 + 3) / 4;
@@ -1473,9 +1150,8 @@ extern "C" int scat_conv1x1_s1_bnb(const float* g, const float* z, const float* 
     dc.p = dx; dc.mode = 1; dc.I = M; dc.J = d.npix; dc.C = M; dc.HW = HW; dc.dHW = FastDiv::make(HW);
     dc.accumulate = accumulate; dc.n = (int64_t)B * M * HW;
     const int cfg = M > 64 ? 0 : 1;
-    set_kernel_label("conv1x1_split_%sx32_bnb", cfg == 0 ? "128x128" : "64x128");
-    if (cfg == 0) launch_pw_split<4, 128, false, true>(d, dc, st);
-    else launch_pw_split<2, 128, false, true>(d, dc, st);
+    set_kernel_label("conv1x1_split_%sx32_bnb", pw_tile_name(cfg));
+    launch_pw_split_cfg<true>(cfg, false, d, dc, st);
     SCAT_LAUNCH_CHECK("scat_conv1x1_s1_bnb");
     return SCAT_OK;
 }
@@ -1490,11 +1166,9 @@ extern "C" int64_t scat_conv1x1_s1_ws(int M, int C) { return (int64_t)M * ((C + 
 extern "C" int scat_conv1x1_s1(const float* src, const float* w, float* dst, int B, int C, int HW, int M,
                                int transposed, const float* bias, const float* in_scale, const float* in_shift,
                                int in_relu, int accumulate, void* ws, int64_t ws_bytes, int w_ready, void* stream) {
-    SkDisarm sk_guard;      // an armed stream-K scratch is this call's or nobody's
     SCAT_REQUIRE(src && w && dst, SCAT_E_ARG, "scat_conv1x1_s1: null pointer");
     SCAT_REQUIRE(!w_ready || math_mode() == 1, SCAT_E_ARG, "scat_conv1x1_s1: prepared weights exist for split products only");
     SCAT_REQUIRE(ws && ws_bytes >= scat_conv1x1_s1_ws(M, C), SCAT_E_WORKSPACE, "scat_conv1x1_s1: workspace too small");
-    const float* a = w;
     SCAT_REQUIRE(B > 0 && C > 0 && HW > 0 && M > 0, SCAT_E_SHAPE, "scat_conv1x1_s1: non-positive dimension");
     SCAT_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), SCAT_E_ARG, "scat_conv1x1_s1: scale/shift pair");
     SCAT_REQUIRE(C % 16 == 0, SCAT_E_SHAPE, "scat_conv1x1_s1: channels must be a multiple of 16");
@@ -1505,20 +1179,15 @@ extern "C" int scat_conv1x1_s1(const float* src, const float* w, float* dst, int
     SCAT_REQUIRE(fits_i32((int64_t)B * C * HW * 4) && fits_i32((int64_t)B * M * HW * 4) && fits_i32((int64_t)M * C * 4),
                  SCAT_E_SHAPE, "scat_conv1x1_s1: tensor exceeds 32-bit byte offsets");
     hipStream_t st = (hipStream_t)stream;
-    PwDesc d{};
-    d.src = src; d.w = a; d.scale = in_scale; d.shift = in_shift; d.relu = in_scale ? in_relu : 0;
-    d.C = C; d.M = M; d.HW = HW; d.npix = B * HW; d.dHW = FastDiv::make(HW);
-    d.ntap = 1; d.KWt = 1; d.a = 1; d.tb = 1; d.c0y = 0; d.c0x = 0; d.H = 1; d.W = HW; d.OW = HW; d.OHW = HW;
-    d.dOHW = FastDiv::make(HW); d.dOW = FastDiv::make(HW);
-    d.nsrc = (int64_t)B * C * HW; d.nw = (int64_t)M * C;
-    d.variant = tuning();
+    PwDesc d = pw_desc(B, C, HW, M);
+    d.src = src; d.w = w; d.scale = in_scale; d.shift = in_shift; d.relu = in_scale ? in_relu : 0;
+    d.nw = (int64_t)M * C;
     OutDesc dc{};
     dc.p = dst; dc.mode = 1; dc.I = M; dc.J = d.npix; dc.C = M; dc.HW = HW; dc.dHW = FastDiv::make(HW);
     dc.bias = bias; dc.bias_mode = bias ? 1 : 0; dc.accumulate = accumulate; dc.n = (int64_t)B * M * HW;
     auto tiles = [&](int bm, int bn) { return (int64_t)cdiv(M, bm) * cdiv(d.npix, bn); };
     int cfg = (M > 64 && tiles(128, 128) >= 1024) ? 0 : 2;   // measured: 64x128 never wins at batch 96
     if (tuning() >= 1 && tuning() <= 3) cfg = tuning() - 1;
-    static const char* const names[] = {"128x128", "64x128", "64x64"};
     const int64_t nel = (int64_t)M * ((C + 15) / 16 * 16);
     const int rblocks = (int)((nel + 255) / 256 < 2048 ? (nel + 255) / 256 : 2048);
     if (math_mode() == 1) {
@@ -1539,97 +1208,19 @@ extern "C" int scat_conv1x1_s1(const float* src, const float* w, float* dst, int
         if (pc < 0) pc = (cfg == 0 && M >= 256 && tiles(128, 128) >= 257 && tiles(128, 128) < 330) ? 6 : 0;
         // wide form: pointwise, whole pixel quads inside one image, 16-byte aligned planes, NCHW output
         const bool w4ok = HW % 4 == 0 && ((uintptr_t)dst & 15) == 0 && (!bias || dc.bias_mode == 1);
-#ifdef SCAT_DIAG     // negative results kept for A/B runs in the tools build only: barrier-free ring, 16x16x32 consumers
-        if (cfg == 0 && pc == 8 && M >= 256) {
-            set_kernel_label("conv1x1_split_pcring_256x128x32%s", in_scale ? "_tf" : "");
-            if (in_scale) launch_pw_pc<1, true, 0, false, 8, false, 6>(d, dc, st);
-            else launch_pw_pc<1, false, 0, false, 8, false, 6>(d, dc, st);
-            SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
-            return SCAT_OK;
-        }
-        if (cfg == 0 && pc == 7 && dc.mode == 1 && (!bias || dc.bias_mode == 1)) {
-            set_kernel_label("conv1x1_split_pc16_128x128x32%s", in_scale ? "_tf" : "");
-            if (in_scale) launch_pw_pc<1, true, 0, false, 4, true>(d, dc, st);
-            else launch_pw_pc<1, false, 0, false, 4, true>(d, dc, st);
-            SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
-            return SCAT_OK;
-        }
-#else
-        if (pc != 5 && pc != 6) pc = 0;      // the shipped library has the two forms the default rule picks, nothing else
-#endif
         if (cfg == 0 && (pc == 5 || pc == 6) && M >= 256) {
             const bool wide = pc == 6 && w4ok;
             set_kernel_label("conv1x1_split_pc%s256x128x32%s", wide ? "4_" : "8w_", in_scale ? "_tf" : "");
             if (wide) {
-                if (in_scale) launch_pw_pc<1, true, 0, true, 8>(d, dc, st); else launch_pw_pc<1, false, 0, true, 8>(d, dc, st);
+                if (in_scale) launch_pw_pc<true, true>(d, dc, st); else launch_pw_pc<false, true>(d, dc, st);
             } else {
-                if (in_scale) launch_pw_pc<1, true, 0, false, 8>(d, dc, st); else launch_pw_pc<1, false, 0, false, 8>(d, dc, st);
+                if (in_scale) launch_pw_pc<true, false>(d, dc, st); else launch_pw_pc<false, false>(d, dc, st);
             }
             SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
             return SCAT_OK;
         }
-#ifdef SCAT_DIAG     // four-consumer producer/consumer forms: no gain over the plain kernel, tools build only
-        if (cfg == 0 && pc >= 3 && pc <= 4 && w4ok) {
-            const bool big = pc == 4 && M >= 256;
-            set_kernel_label("conv1x1_split_pc4_%dx128x32%s", big ? 256 : 128, in_scale ? "_tf" : "");
-#ifdef SCAT_DIAG
-            if (!in_scale && !big && tuning() >= 100) {      // ablation variants (SCAT_TUNE=100+DIAG), diag build only
-                switch (tuning() - 100) {
-                case 1: launch_pw_pc<1, false, 1, true>(d, dc, st); break;
-                case 2: launch_pw_pc<1, false, 2, true>(d, dc, st); break;
-                case 4: launch_pw_pc<1, false, 4, true>(d, dc, st); break;
-                case 8: launch_pw_pc<1, false, 8, true>(d, dc, st); break;
-                case 11: launch_pw_pc<1, false, 11, true>(d, dc, st); break;
-                case 20: launch_pw_pc<1, false, 20, true>(d, dc, st); break;
-                default: launch_pw_pc<1, false, 0, true>(d, dc, st);
-                }
-            } else
-#endif
-            if (in_scale) {
-                if (big) launch_pw_pc<2, true, 0, true>(d, dc, st); else launch_pw_pc<1, true, 0, true>(d, dc, st);
-            } else {
-                if (big) launch_pw_pc<2, false, 0, true>(d, dc, st); else launch_pw_pc<1, false, 0, true>(d, dc, st);
-            }
-            SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
-            return SCAT_OK;
-        }
-        if (cfg == 0 && pc && pc <= 4) {
-            const bool big = (pc == 2 || pc == 4) && M >= 256;
-            set_kernel_label("conv1x1_split_pc%dx128x32%s", big ? 256 : 128, in_scale ? "_tf" : "");
-#ifdef SCAT_DIAG
-            if (!in_scale && !big && tuning() >= 100) {      // ablation variants (SCAT_TUNE=100+DIAG), diag build only
-                switch (tuning() - 100) {
-                case 1: launch_pw_pc<1, false, 1>(d, dc, st); break;
-                case 2: launch_pw_pc<1, false, 2>(d, dc, st); break;
-                case 4: launch_pw_pc<1, false, 4>(d, dc, st); break;
-                case 8: launch_pw_pc<1, false, 8>(d, dc, st); break;
-                case 16: launch_pw_pc<1, false, 16>(d, dc, st); break;
-                case 17: launch_pw_pc<1, false, 17>(d, dc, st); break;
-                case 3: launch_pw_pc<1, false, 3>(d, dc, st); break;
-                case 11: launch_pw_pc<1, false, 11>(d, dc, st); break;
-                case 20: launch_pw_pc<1, false, 20>(d, dc, st); break;
-                default: launch_pw_pc<1, false>(d, dc, st);
-                }
-                SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
-                return SCAT_OK;
-            }
-#endif
-            if (in_scale) { if (big) launch_pw_pc<2, true>(d, dc, st); else launch_pw_pc<1, true>(d, dc, st); }
-            else { if (big) launch_pw_pc<2, false>(d, dc, st); else launch_pw_pc<1, false>(d, dc, st); }
-            SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
-            return SCAT_OK;
-        }
-#endif
-        set_kernel_label("conv1x1_split_%sx32%s", names[cfg], in_scale ? "_tf" : "");
-        if (in_scale) {
-            if (cfg == 0) launch_pw_split<4, 128, true>(d, dc, st);
-            else if (cfg == 1) launch_pw_split<2, 128, true>(d, dc, st);
-            else launch_pw_split<2, 64, true>(d, dc, st);
-        } else {
-            if (cfg == 0) launch_pw_split<4, 128, false>(d, dc, st);
-            else if (cfg == 1) launch_pw_split<2, 128, false>(d, dc, st);
-            else launch_pw_split<2, 64, false>(d, dc, st);
-        }
+        set_kernel_label("conv1x1_split_%sx32%s", pw_tile_name(cfg), in_scale ? "_tf" : "");
+        launch_pw_split_cfg(cfg, in_scale != nullptr, d, dc, st);
         SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
         return SCAT_OK;
     }
@@ -1638,7 +1229,7 @@ extern "C" int scat_conv1x1_s1(const float* src, const float* w, float* dst, int
         d.w = (const float*)ws;
     }
     const bool v4 = HW % 4 == 0;
-    set_kernel_label("conv1x1_pw_%sx32%s%s", names[cfg], v4 ? "_b4" : "", in_scale ? "_tf" : "");
+    set_kernel_label("conv1x1_pw_%sx32%s%s", pw_tile_name(cfg), v4 ? "_b4" : "", in_scale ? "_tf" : "");
     if (v4) {
         if (in_scale) launch_pw_cfg<true, true>(cfg, d, dc, st);
         else launch_pw_cfg<true, false>(cfg, d, dc, st);
@@ -1674,11 +1265,8 @@ extern "C" int scat_gemm_split(const float* a, int a_transposed, const float* b,
                  SCAT_E_SHAPE, "scat_gemm_split: operand exceeds 32-bit byte offsets");
     hipStream_t st = (hipStream_t)stream;
     wprep_launch(wprep_job(a, ws, M, K, a_transposed, 1, 1, 1, 1, 0, 0, 1), st);
-    PwDesc d{};
-    d.src = b; d.C = K; d.M = M; d.HW = N; d.npix = N; d.dHW = FastDiv::make(N);
-    d.ntap = 1; d.KWt = 1; d.a = 1; d.tb = 1; d.c0y = 0; d.c0x = 0; d.H = 1; d.W = N; d.OW = N; d.OHW = N;
-    d.dOHW = FastDiv::make(N); d.dOW = FastDiv::make(N);
-    d.nsrc = (int64_t)K * N; d.variant = tuning();
+    PwDesc d = pw_desc(1, K, N, M);
+    d.src = b;
     const int64_t nel = (int64_t)M * ((K + 15) / 16 * 16);
     d.w = (const float*)ws;
     d.nw = (nel * 6 + 3) / 4;
@@ -1689,11 +1277,8 @@ extern "C" int scat_gemm_split(const float* a, int a_transposed, const float* b,
     auto tiles = [&](int bm, int bn) { return (int64_t)cdiv(M, bm) * cdiv(N, bn); };
     int cfg = tiles(128, 128) >= 512 ? 0 : (tiles(64, 128) >= 512 ? 1 : 2);
     if (tuning() >= 1 && tuning() <= 3) cfg = tuning() - 1;
-    static const char* const names[] = {"128x128", "64x128", "64x64"};
-    set_kernel_label("gemm_split_%sx32", names[cfg]);
-    if (cfg == 0) launch_pw_split<4, 128, false>(d, dc, st);
-    else if (cfg == 1) launch_pw_split<2, 128, false>(d, dc, st);
-    else launch_pw_split<2, 64, false>(d, dc, st);
+    set_kernel_label("gemm_split_%sx32", pw_tile_name(cfg));
+    launch_pw_split_cfg(cfg, false, d, dc, st);
     SCAT_LAUNCH_CHECK("scat_gemm_split");
     return SCAT_OK;
 }
@@ -1722,25 +1307,5 @@ extern "C" int scat_transpose2d(const float* src, float* dst, int R, int C, void
     hipLaunchKernelGGL(transpose2d_kernel, dim3(cdiv(C, 32), cdiv(R, 32)), dim3(256), 0, (hipStream_t)stream, src, dst,
                        R, C);
     SCAT_LAUNCH_CHECK("scat_transpose2d");
-    return SCAT_OK;
-}
-
-/* Stream-K scratch for the pointwise kernels (include/scat_hip.h).  Consumed by the next qualifying launch of this host
- * thread; a launch that does not qualify (few tiles, taps, scratch too small) disarms it and runs one tile per
- * workgroup. */
-extern "C" int64_t scat_streamk_bytes(void) { return scat::SK_BYTES; }
-extern "C" int scat_streamk_arm(void* buf, int64_t bytes) {
-    scat::g_sk.buf = buf;
-    scat::g_sk.bytes = buf ? bytes : 0;
-    return SCAT_OK;
-}
-extern "C" int scat_streamk_error(const void* buf, int64_t bytes, void* stream) {
-    SCAT_REQUIRE(buf && bytes >= scat::SK_BYTES, SCAT_E_ARG, "scat_streamk_error: not a stream-K scratch buffer");
-    uint32_t v = 0;
-    hipError_t e = hipMemcpyAsync(&v, (const char*)buf + scat::SK_PART + scat::SK_G * 4, 4, hipMemcpyDeviceToHost,
-                                  (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    SCAT_REQUIRE(e == hipSuccess, SCAT_E_LAUNCH, "scat_streamk_error: %s", hipGetErrorString(e));
-    SCAT_REQUIRE(v == 0, SCAT_E_LAUNCH, "a stream-K workgroup gave up waiting for a partial tile (device error word %u)", v);
     return SCAT_OK;
 }

@@ -35,8 +35,7 @@ def test_header_declares_the_path():
                                                 "scat_set_math_mode",
                                                 # host-side state of the NEXT launch of this thread, no device work
                                                 "scat_epilogue_stats_arm", "scat_epilogue_stats_arm_shift", "scat_epilogue_stats_groups",
-                                                "scat_epilogue_bnb_arm", "scat_epilogue_bnb_groups",
-                                                "scat_streamk_arm"):
+                                                "scat_epilogue_bnb_arm", "scat_epilogue_bnb_groups"):
             assert args[-1][1] == "stream", name
     # every prototype cites the reference file it replaces somewhere in the header
     src = open(os.path.join(ROOT, "include", "scat_hip.h")).read()
@@ -49,6 +48,9 @@ def test_library_exports_every_symbol(built):
     L = lib()
     for name in parse_header():
         assert hasattr(L.cdll, name), name
+        assert "streamk" not in name, name
+    for name in ("scat_streamk_bytes", "scat_streamk_arm", "scat_streamk_error"):
+        assert not hasattr(L.cdll, name), name
     assert L.scat_version() >= 100
     assert isinstance(L.scat_last_kernel(), bytes)
 

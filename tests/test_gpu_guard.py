@@ -675,25 +675,6 @@ def _c17(t):
     t.out("dx_acc", acc, lambda: dx_ref() + base.double())
 
 
-# stream-K scratch protocol at a launch too small to qualify (fewer than 256 tiles): the arm is consumed, the kernel is
-# the one-tile-per-workgroup one, the scratch and its guards are untouched and scat_streamk_error reads its error word
-@case("streamk_protocol", ("scat_streamk_arm", "scat_streamk_error", "scat_conv1x1_s1"), 2e-5, maths=(1,))
-def _c18(t):
-    x = t.once("x", lambda: R(290, (2, 32, 6, 6)))
-    w = t.once("w", lambda: R(291, (64, 32, 1, 1), std=0.25))
-    n = int(t.lib.scat_streamk_bytes())
-    sk = t.arena.place(torch.zeros(n, dtype=torch.uint8), 0, name="streamk_scratch", out=True)
-    t.lib.scat_streamk_arm(P(sk), n)
-    try:
-        y = t.ops.conv2d_fwd(t.inp(x, "x"), t.inp(w, "w"), 1, 0)
-    finally:
-        t.lib.scat_streamk_arm(0, 0)      # (a skewed x never reaches the pointwise entry point that would consume the arm)
-    assert not t.label().endswith("_sk")
-    t.lib.scat_streamk_error(P(sk), n, t.stream())
-    assert not bool(sk.any())
-    t.out("y", y, lambda: _conv_ref(x, w, None, 1, 0))
-
-
 # ====================================================================================================== BatchNorm
 
 def _bn_inputs(t, B, C, H, W, seed):

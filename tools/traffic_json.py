@@ -39,14 +39,14 @@ def main():
     write = mean_by_kernel(sys.argv[2], "WRITE_SIZE")
     out = {}
     for k in sorted(set(fetch) & set(write)):
-        if not any(t in k for t in ("gemm<", "split_kernel", "halo_kernel", "conv1x1_kernel", "pc_kernel", "pw_kernel", "sk_kernel", "rows_kernel", "rows64_kernel", "vit_", "bn_")):
+        if not any(t in k for t in ("gemm<", "split_kernel", "halo_kernel", "conv1x1_kernel", "pc_kernel", "pw_kernel", "rows_kernel", "rows64_kernel", "vit_", "bn_")):
             continue
         f, n = fetch[k]
         w, _ = write[k]
-        narrow = k.startswith("conv1x1_split_kernel") or k.startswith("conv1x1_sk_kernel")
-        if k.startswith("conv1x1_pc_kernel"):          # <MI, TF, DIAG, W4, ...>: the W4 form loads 16 bytes per lane
-            args = k[k.index("<") + 1:].split(",")
-            narrow = len(args) > 3 and args[3] == "f"
+        narrow = k.startswith("conv1x1_split_kernel")
+        if k.startswith("conv1x1_pc_kernel"):          # <TF, W4>: the W4 form loads 16 bytes per lane
+            args = k[k.index("<") + 1:].rstrip(">").split(",")
+            narrow = len(args) > 1 and args[1] == "f"
         factor = 1.0 / 0.565 if narrow else 2.0
         out[k] = {"FETCH_SIZE_bytes_per_launch_raw": int(f * 1024), "WRITE_SIZE_bytes_per_launch": int(w * 1024),
                   "fetch_factor": round(factor, 3),
