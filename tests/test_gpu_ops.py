@@ -1028,6 +1028,16 @@ def _pc_case(ops, B, cin, cout, H, W, expect):
     assert rel_err(dxta, dxt_ref + base.cpu().double()) < 2e-5
 
 
+PC_EXACT_SHAPES = [PC_SHAPES[0], PC_SHAPES[4]]        # full pixel quads; HW % 4 != 0 (scalar pixels in both forms)
+
+
+def _pc_exact_case(ops, B, cin, cout, H, W, expect):
+    """the same roles on exact-sum data (tests/test_gpu_exact_split.py): every result bit-for-bit the fp64 answer, so a
+    lost or mis-paired term of the six shows in this form too"""
+    import test_gpu_exact_split as X
+    X.pc_exact_case(ops, B, cin, cout, H, W, expect)
+
+
 @pytest.mark.parametrize("pc", [5, 6])
 def test_conv1x1_producer_consumer_forms(pc):
     import subprocess
@@ -1038,6 +1048,8 @@ def test_conv1x1_producer_consumer_forms(pc):
             "for a in T.PC_SHAPES:\n"
             "    wide = %d == 6 and (a[3] * a[4]) %% 4 == 0\n"
             "    T._pc_case(ops, *a, 'conv1x1_split_pc4_256' if wide else 'conv1x1_split_pc8w_256')\n"
+            "    if a in T.PC_EXACT_SHAPES:\n"
+            "        T._pc_exact_case(ops, *a, 'conv1x1_split_pc4_256' if wide else 'conv1x1_split_pc8w_256')\n"
             "print('PC OK')\n") % (root, os.path.join(root, "tests"), pc)
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SCAT_PC=str(pc)), capture_output=True, text=True,
                        timeout=600, cwd=root)
