@@ -1072,6 +1072,67 @@ def eval_accumulate(out, labels, thresholds, keep=None, record=None, want_per_sa
     return record, per_sample, aligned
 
 
+RENDER_PROJ_WORDS = 8   # 32-bit words per projected vertex (layout: include/scat_render.h scat_render_project)
+
+
+def _render_chk(what, *specs):
+    """specs: (tensor, dtype, shape with None for a free extent); contiguous GPU tensors or ScatError"""
+    for t, dt, shape in specs:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ScatError(f"{what} needs GPU tensors (no CPU fallback on the product path)")
+        if not (t.dtype == dt and t.is_contiguous() and t.dim() == len(shape)
+                and all(s is None or s == n for s, n in zip(shape, t.shape))):
+            raise ScatError(f"{what} needs a contiguous {dt} tensor of shape {list(shape)}, got {t.dtype} {tuple(t.shape)} "
+                            f"contiguous={t.is_contiguous()}")
+
+
+def render_project(verts, cam, faces, vf_off, vf_idx, H, W):
+    """verts [B,V,3] fp32, cam [B,3] fp32, the topology (faces [F,3], vf_off [V+1], vf_idx [3F], int32) -> proj [B,V,8]
+    int32 words: snapped X, Y, z, unit normal, validity, spare (include/scat_render.h scat_render_project)"""
+    _render_chk("render_project", (verts, torch.float32, (None, None, 3)), (faces, torch.int32, (None, 3)))
+    B, V, F = verts.shape[0], verts.shape[1], faces.shape[0]
+    _render_chk("render_project", (cam, torch.float32, (B, 3)), (vf_off, torch.int32, (V + 1,)), (vf_idx, torch.int32, (3 * F,)))
+    proj = torch.empty((B, V, RENDER_PROJ_WORDS), dtype=torch.int32, device=verts.device)
+    lib().scat_render_project(_p(verts), _p(cam), _p(faces), _p(vf_off), _p(vf_idx), _p(proj), B, V, F, int(H), int(W),
+                              _stream())
+    return proj
+
+
+def render_raster(proj, faces, H, W, img=None, lights=None, base_rgb=(1.0, 1.0, 0.9), ambient=0.3, cull=False,
+                  want_rgb=True):
+    """proj [B,V,8] int32 from render_project, faces [F,3] int32, img [B,H,W,3] uint8 or None, lights [L,4] fp32 or None
+    -> (face_id [B,H,W] int32, depth [B,H,W] fp32, rgb [B,H,W,3] uint8 | None) (include/scat_render.h scat_render_raster)"""
+    _render_chk("render_raster", (proj, torch.int32, (None, None, RENDER_PROJ_WORDS)), (faces, torch.int32, (None, 3)))
+    B, H, W = proj.shape[0], int(H), int(W)
+    if img is not None:
+        _render_chk("render_raster", (img, torch.uint8, (B, H, W, 3)))
+    if lights is not None:
+        _render_chk("render_raster", (lights, torch.float32, (None, 4)))
+    dev = proj.device
+    face_id = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    rgb = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) if want_rgb else None
+    lib().scat_render_raster(_p(proj), _p(faces), _p(img), _p(lights), _p(face_id), _p(depth), _p(rgb), B, proj.shape[1],
+                             faces.shape[0], H, W, 0 if lights is None else lights.shape[0], float(base_rgb[0]),
+                             float(base_rgb[1]), float(base_rgb[2]), float(ambient), int(bool(cull)), _stream())
+    return face_id, depth, rgb
+
+
+def render_skeleton(rgb, j2d, bones, colors, radius_bone, radius_joint):
+    """rgb [B,H,W,3] uint8 painted in place; j2d [B,J,2] fp32 pixels, bones [NB,2] int32 or None, colors [NB+J,3] uint8
+    (include/scat_render.h scat_render_skeleton)"""
+    _render_chk("render_skeleton", (rgb, torch.uint8, (None, None, None, 3)))
+    _render_chk("render_skeleton", (j2d, torch.float32, (rgb.shape[0], None, 2)))
+    B = rgb.shape[0]
+    J, NB = j2d.shape[1], 0 if bones is None else bones.shape[0]
+    if bones is not None:
+        _render_chk("render_skeleton", (bones, torch.int32, (None, 2)))
+    _render_chk("render_skeleton", (colors, torch.uint8, (NB + J, 3)))
+    lib().scat_render_skeleton(_p(j2d), _p(bones), _p(colors), _p(rgb), B, J, NB, rgb.shape[1], rgb.shape[2],
+                               float(radius_bone), float(radius_joint), _stream())
+    return rgb
+
+
 def fuse_sum(terms, relu=True):
     """relu?(sum of terms), terms = [(tensor [B,C,H>>k,W>>k], scale|None, shift|None, k)] in the order they are added
     (one pass; include/scat_hip.h scat_fuse_sum)."""
