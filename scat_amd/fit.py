@@ -1,0 +1,157 @@
+"""The inverse of the MANO layer on the device (include/scat_mano_fit.h, csrc/mano_fit.hip): pose, shape and a
+similarity fitted to 21 joints by Levenberg-Marquardt, one launch for the whole batch.  It connects the headline networks,
+which predict [B,66] (camera + 21 joints), to ManoLayer and MeshRenderer, which want the MANO parameters:
+
+    fitter = ManoFitter(ManoModel.synthetic(1).to("cuda"))
+    res = fitter.fit_outputs(out66)                    # FitResult(rots, poses, betas, trans, scale, cost, accepted)
+    verts = fitter.mesh(res)                           # [B,V,3] in the frame of the predicted joints
+    frames = renderer.render(verts, out66[:, :3])      # with the predicted camera
+
+There is no CPU fallback: CPU tensors raise ScatError."""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from ._lib import ScatError, lib
+from .mano import BETAS, POSE, ManoModel, _model_args, _need_gpu, mano_fwd
+from .ops import _p, _stream
+
+UNKNOWNS = 62                  # rots 3, poses 45, betas 10, trans 3, log_scale 1: SCAT_FIT_UNKNOWNS
+MAX_ITERS = 64                 # SCAT_FIT_MAX_ITERS
+ALL_FREE = (1 << UNKNOWNS) - 1
+SLICES = {"rots": slice(0, 3), "poses": slice(3, 48), "betas": slice(48, 58), "trans": slice(58, 61), "log_scale": slice(61, 62)}
+
+
+def free_mask(**free):
+    """the mask with the named groups frozen: free_mask(betas=False, log_scale=False)"""
+    m = ALL_FREE
+    for k, on in free.items():
+        s = SLICES[k]
+        if not on:
+            m &= ~(((1 << (s.stop - s.start)) - 1) << s.start)
+    return m
+
+
+class FitResult(NamedTuple):
+    rots: torch.Tensor       # [B,3]
+    poses: torch.Tensor      # [B,45]
+    betas: torch.Tensor      # [B,10]
+    trans: torch.Tensor      # [B,3]
+    scale: torch.Tensor      # [B]
+    cost: torch.Tensor       # [B], +inf for a sample whose targets were not finite
+    accepted: torch.Tensor   # [B] int32
+    p: torch.Tensor          # [B,62]: the five groups as the kernel holds them (log_scale last)
+
+
+def _check_model(what, model, ref):
+    if model.device is None or model.device != ref.device:
+        raise ScatError(f"{what}: the model is on {model.device}, the inputs on {ref.device}: call ManoModel.to first")
+
+
+def mano_joints_jac(model, rots, poses, betas):
+    """-> (joints [B,21,3], jac [B,63,58]): the 21 joints of mano_fwd and d joints / d (rots, poses, betas), one launch"""
+    _need_gpu("mano_joints_jac", rots, poses, betas)
+    _check_model("mano_joints_jac", model, rots)
+    B = rots.shape[0]
+    if B == 0 or tuple(rots.shape) != (B, 3) or tuple(poses.shape) != (B, POSE) or tuple(betas.shape) != (B, BETAS):
+        raise ScatError(f"mano_joints_jac needs rots [B,3], poses [B,45], betas [B,10] with B >= 1, got {tuple(rots.shape)}, "
+                        f"{tuple(poses.shape)}, {tuple(betas.shape)}")
+    if not all(t.dtype == torch.float32 for t in (rots, poses, betas)):
+        raise ScatError("mano_joints_jac needs fp32 tensors")
+    rots, poses, betas = rots.contiguous(), poses.contiguous(), betas.contiguous()
+    joints = torch.empty((B, 21, 3), dtype=torch.float32, device=rots.device)
+    jac = torch.empty((B, 63, 58), dtype=torch.float32, device=rots.device)
+    lib().scat_mano_joints_jac(*_model_args(model), _p(rots), _p(poses), _p(betas), _p(joints), _p(jac), B, model.V,
+                               model.parents_packed, *model.tips, _stream())
+    return joints, jac
+
+
+def mano_fit(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose, w_beta, free=ALL_FREE):
+    """scat_mano_fit as it is declared: targets [B,21,3], weights [B,21] or None, joint_map int32 [21] on the device,
+    p [B,62] (read when init = 0, written) -> (cost [B], accepted [B] int32)"""
+    B = targets.shape[0]
+    cost = torch.empty((B,), dtype=torch.float32, device=targets.device)
+    accepted = torch.empty((B,), dtype=torch.int32, device=targets.device)
+    lib().scat_mano_fit(*_model_args(model), _p(targets), _p(weights), _p(joint_map), _p(p), _p(cost), _p(accepted), B, model.V,
+                        model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose), float(w_beta),
+                        int(free), _stream())
+    return cost, accepted
+
+
+class ManoFitter:
+    """Fits rots, poses, betas, a translation and a scale to 21 joints.  model: a ManoModel already moved to the device.
+    joint_map: a permutation of 0..20, target joint j is the model's joint joint_map[j] (None: the model's own order).
+    w_pose, w_beta: the priors' weights; for targets in metres they are of the 1e-6 order, larger ones pull a 0.1 m hand
+    millimetres off its targets.  lambda0: the first damping."""
+
+    def __init__(self, model: ManoModel, joint_map=None, w_pose=1e-6, w_beta=1e-6, iters=20, lambda0=1e-3):
+        jm = list(range(21)) if joint_map is None else [int(j) for j in joint_map]
+        if sorted(jm) != list(range(21)):
+            raise ScatError("ManoFitter: joint_map must be a permutation of 0..20")
+        if not 1 <= int(iters) <= MAX_ITERS:
+            raise ScatError(f"ManoFitter: {iters} iterations outside 1..{MAX_ITERS}")
+        if w_pose < 0 or w_beta < 0 or not lambda0 > 0:
+            raise ScatError("ManoFitter: the priors' weights must not be negative and lambda0 must be positive")
+        self.model, self.joint_map = model, tuple(jm)
+        self.joint_map_d = None      # uploaded by the first fit
+        self.w_pose, self.w_beta, self.iters, self.lambda0 = float(w_pose), float(w_beta), int(iters), float(lambda0)
+
+    def fit(self, joints, weights=None, init=None, free=ALL_FREE, iters=None):
+        """joints [B,21,3] fp32 -> FitResult.  weights: [B,21] or None (all ones).  init: None for the Procrustes start, or
+        p [B,62] / a FitResult to start from (it is not modified).  free: bit i clear freezes unknown i (free_mask()).
+        A sample whose targets or weights are not finite, or that has a negative weight, is not fitted: its cost is +inf,
+        its accepted count 0 and its p the start (zeros for the Procrustes start)."""
+        _need_gpu("ManoFitter.fit", joints, *(() if weights is None else (weights,)))
+        _check_model("ManoFitter.fit", self.model, joints)
+        B = joints.shape[0]
+        if B == 0 or tuple(joints.shape) != (B, 21, 3) or joints.dtype != torch.float32:
+            raise ScatError(f"ManoFitter.fit needs fp32 joints [B,21,3] with B >= 1, got {joints.dtype} {tuple(joints.shape)}")
+        if weights is not None and (tuple(weights.shape) != (B, 21) or weights.dtype != torch.float32):
+            raise ScatError(f"ManoFitter.fit needs fp32 weights [{B},21], got {weights.dtype} {tuple(weights.shape)}")
+        if init is None:
+            p = torch.empty((B, UNKNOWNS), dtype=torch.float32, device=joints.device)
+        else:
+            p0 = init.p if isinstance(init, FitResult) else init
+            _need_gpu("ManoFitter.fit", p0)
+            if tuple(p0.shape) != (B, UNKNOWNS) or p0.dtype != torch.float32:
+                raise ScatError(f"ManoFitter.fit needs an fp32 start [{B},{UNKNOWNS}], got {p0.dtype} {tuple(p0.shape)}")
+            p = p0.clone().contiguous()
+        iters = self.iters if iters is None else int(iters)
+        if not 1 <= iters <= MAX_ITERS:
+            raise ScatError(f"ManoFitter.fit: {iters} iterations outside 1..{MAX_ITERS}")
+        if not 0 <= int(free) <= ALL_FREE:
+            raise ScatError(f"ManoFitter.fit: free has bits above {UNKNOWNS - 1} set")
+        cost, accepted = mano_fit(self.model, joints.contiguous(), None if weights is None else weights.contiguous(),
+                                  self._map_on(joints.device), p, iters, 0 if init is not None else 1,
+                                  self.lambda0, self.w_pose, self.w_beta, free)
+        return FitResult(p[:, 0:3], p[:, 3:48], p[:, 48:58], p[:, 58:61], torch.exp(p[:, 61]), cost, accepted, p)
+
+    def _map_on(self, device):
+        if self.joint_map_d is None or self.joint_map_d.device != device:
+            self.joint_map_d = torch.tensor(self.joint_map, dtype=torch.int32, device=device)
+        return self.joint_map_d
+
+    def fit_outputs(self, out66, weights=None):
+        """out66 [B,66]: the network's camera and 21 root-relative joints; the joints are fitted, the camera is the
+        caller's to pass on to the renderer"""
+        _need_gpu("ManoFitter.fit_outputs", out66)
+        if out66.dim() != 2 or out66.shape[1] != 66:
+            raise ScatError(f"fit_outputs needs the network's output [B,66], got {tuple(out66.shape)}")
+        return self.fit(out66.detach()[:, 3:].reshape(-1, 21, 3).contiguous(), weights)
+
+    def joints(self, result):
+        """the fitted joints [B,21,3] in the targets' frame and order"""
+        return self._posed(result)[0]
+
+    def mesh(self, result):
+        """the fitted mesh [B,V,3] in the targets' frame: scale x vertices + trans, through scat_mano_fwd"""
+        return self._posed(result)[1]
+
+    def _posed(self, r):
+        _need_gpu("ManoFitter.mesh", r.p)
+        _check_model("ManoFitter.mesh", self.model, r.p)
+        out = mano_fwd(self.model, r.rots.contiguous(), r.poses.contiguous(), r.betas.contiguous())
+        out = r.scale[:, None, None] * out + r.trans[:, None, :]
+        return out[:, :21][:, self._map_on(out.device).long()], out[:, 21:].contiguous()
