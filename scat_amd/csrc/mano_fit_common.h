@@ -1,0 +1,344 @@
+// What the two fit kernels share (mano_fit.hip: 3-D joints, quadratic; mano_fit_kp.hip: 2-D keypoints, robust loss, joint
+// limits): the constants, the LDS state of the joints' Jacobian with jac_load_model and jac_eval, the Procrustes start and
+// fit_finite.  mano_fit.hip's header comment has the derivation of the Jacobian's columns.
+#pragma once
+#include "mano_common.h"
+
+#include "../../include/scat_mano_fit.h"
+#include "eval_solve.h"
+
+namespace scat {
+
+constexpr int kFThreads = 256;
+constexpr int kFJoints = kMJ + kMTips;        // 21
+constexpr int kFRows = 3 * kFJoints;          // 63
+constexpr int kFModel = SCAT_FIT_MODEL_UNKNOWNS;   // 58: rots, poses, betas
+constexpr int kFU = SCAT_FIT_UNKNOWNS;        // 62: + trans, log_scale
+constexpr int kFPose = 3 * (kMJ - 1);         // 45
+constexpr float kFLambdaMin = 1e-12f, kFLambdaMax = 1e12f;
+
+struct JacLds {
+    ManoPose s;
+    float tb[kMTips][1 + kMCoef][3];   // the tips' rows of the blend table: template, shapedirs, posedirs
+    float tw[kMTips][kMJ];             // the tips' skinning weights
+    float D[kFPose][9];                // dR_k / dr_m, index 3 (k - 1) + m
+    float Om[kFPose][9];               // RG_parent(k) D RG_k^T
+    float dRg[3][9];                   // dRg / d rots_m
+    float dtb[kMJ][kMBeta][3];         // d t_i / d beta_b
+    float vp[kMTips][3];               // the tips' v_posed
+    float T[kMTips][9];                // the tips' blended rotation
+    float y[kFJoints][3];              // y_i - t_1, un-rotated
+    float x[kFRows];                   // Rg (y_map[j] - y_1): the joints in the caller's order
+    int map[kFJoints];
+    uint32_t anc[kMJ];                 // bit k: k is i or an ancestor of i
+};
+
+// dR/dr_m for R = I + a(t) S(r) + b(t) (r r^T - t I), t = |r|^2: the forward-mode twin of rod_bwd
+__device__ __forceinline__ void rod_fwd(const float r[3], int m, float D[9]) {
+    const float x = r[0], y = r[1], z = r[2];
+    const float t = x * x + y * y + z * z;
+    const RodCoef c = rod_coef(t);
+    const float S[9] = {0.f, -z, y, z, 0.f, -x, -y, x, 0.f};
+    const float rm = r[m], k = 2.f * rm;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float Sm = (i != j && 3 - i - j == m) ? (((3 + j - i) % 3 == 1) ? -1.f : 1.f) : 0.f;   // S(e_m)
+            const float em = ((i == m) ? r[j] : 0.f) + ((j == m) ? r[i] : 0.f) - ((i == j) ? k : 0.f);
+            const float q = r[i] * r[j] - ((i == j) ? t : 0.f);
+            D[3 * i + j] = c.a * Sm + c.b * em + k * (c.da * S[3 * i + j] + c.db * q);
+        }
+}
+
+// once per workgroup: what the tips need of the model, and the ancestor masks
+__device__ void jac_load_model(JacLds& m, const ManoArgs& p) {
+    const int tid = threadIdx.x, V = p.V;
+    constexpr int per = (1 + kMCoef) * 3;
+    for (int w = tid; w < kMTips * per; w += kFThreads) {
+        const int j = w / per, kc = w % per;
+        m.tb[j][kc / 3][kc % 3] = p.blend[(int64_t)kc * V + p.tips.v[j]];
+    }
+    for (int w = tid; w < kMTips * kMJ; w += kFThreads) m.tw[w / kMJ][w % kMJ] = p.weights_t[(w % kMJ) * V + p.tips.v[w / kMJ]];
+    if (tid < kMJ) {
+        uint32_t a = 1u << tid;
+        int c = tid;
+        while (c > 0) {
+            c = mano_parent(p.parents, c);
+            a |= 1u << c;
+        }
+        m.anc[tid] = a;
+    }
+}
+
+// d y_i / d pose (k, m), q = 3 (k - 1) + m
+__device__ __forceinline__ void jac_pose_col(const JacLds& m, int i, int q, int k, float out[3]) {
+    const ManoPose& s = m.s;
+    float Om[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Om[e] = m.Om[q][e];
+    if (i < kMJ) {
+        float d[3] = {0.f, 0.f, 0.f};
+        if (((m.anc[i] >> k) & 1u) && i != k) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[c] = s.t[i][c] - s.t[k][c];
+        }
+        mv(Om, d, out);
+        return;
+    }
+    const int tj = i - kMJ;
+    float u[3] = {0.f, 0.f, 0.f};
+    for (int ii = 1; ii < kMJ; ++ii) {
+        const float w = m.tw[tj][ii];
+        if (!((m.anc[ii] >> k) & 1u) || w == 0.f) continue;
+        float RGi[9], e[3], f[3];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) RGi[c] = s.RG[ii][c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] = m.vp[tj][c] - s.J[ii][c];
+        mv(RGi, e, f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) u[c] += w * (f[c] + (s.t[ii][c] - s.t[k][c]));
+    }
+    float o1[3], o2[3], pd[3] = {0.f, 0.f, 0.f}, T[9];
+    mv(Om, u, o1);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+        const float De = m.D[q][e];
+        T[e] = m.T[tj][e];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pd[c] += m.tb[tj][1 + kMBeta + 9 * (k - 1) + e][c] * De;
+    }
+    mv(T, pd, o2);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = o1[c] + o2[c];
+}
+
+// d y_i / d beta_b
+__device__ __forceinline__ void jac_beta_col(const JacLds& m, const ManoArgs& p, int i, int b, float out[3]) {
+    const ManoPose& s = m.s;
+    if (i < kMJ) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[c] = m.dtb[i][b][c];
+        return;
+    }
+    const int tj = i - kMJ;
+    float u[3] = {0.f, 0.f, 0.f};
+    for (int ii = 0; ii < kMJ; ++ii) {
+        const float w = m.tw[tj][ii];
+        if (w == 0.f) continue;
+        float RGi[9], e[3], f[3];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) RGi[c] = s.RG[ii][c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] = m.tb[tj][1 + b][c] - p.joint_s[(ii * 3 + c) * kMBeta + b];
+        mv(RGi, e, f);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) u[c] += w * (f[c] + m.dtb[ii][b][c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = u[c];
+}
+
+// Joints, and with want_jac the 58 model columns of the Jacobian times `scale`, for the parameters p.rots / p.poses /
+// p.betas of sample b (global memory, or LDS with b = 0).  m.x gets the joints in the order of m.map; J[(3 j + c) ld + q].
+// Called by all threads; begins and ends with a barrier.
+__device__ void jac_eval(JacLds& m, const ManoArgs& p, int64_t b, bool want_jac, float scale, float* J, int ld) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    mano_setup(m.s, p, b);
+    const ManoPose& s = m.s;
+    if (tid < kMTips) {   // mano_vertex from the LDS copy, same order of sums
+        float acc[kMBlendGroup][3];
+#pragma unroll
+        for (int q = 0; q < kMBlendGroup; ++q)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[q][c] = 0.f;
+        for (int k0 = 0; k0 < kMCoef; k0 += kMBlendGroup) {
+#pragma unroll
+            for (int q = 0; q < kMBlendGroup; ++q) {
+                const float ck = s.coef[k0 + q];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[q][c] += ck * m.tb[tid][1 + k0 + q][c];
+            }
+        }
+        float vp[3], T[9], Ta[3] = {0.f, 0.f, 0.f}, x[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vp[c] = m.tb[tid][0][c] + (((acc[0][c] + acc[1][c]) + (acc[2][c] + acc[3][c])) + acc[4][c]);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) T[e] = 0.f;
+        for (int i = 0; i < kMJ; ++i) {
+            const float w = m.tw[tid][i];
+#pragma unroll
+            for (int e = 0; e < 9; ++e) T[e] += w * s.RG[i][e];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Ta[c] += w * s.a[i][c];
+        }
+        mv(T, vp, x);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            m.vp[tid][c] = vp[c];
+            m.y[kMJ + tid][c] = (x[c] + Ta[c]) - s.t[1][c];
+        }
+#pragma unroll
+        for (int e = 0; e < 9; ++e) m.T[tid][e] = T[e];
+    } else if (tid >= 64 && tid < 64 + kMJ) {
+        const int i = tid - 64;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m.y[i][c] = s.t[i][c] - s.t[1][c];
+    }
+    if (want_jac) {
+        if (tid >= 128 && tid < 128 + kFPose) {
+            const int q = tid - 128, k = 1 + q / 3, pa = mano_parent(p.parents, k);
+            float r[3], D[9], RGp[9], RGk[9], t1[9], Om[9];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = s.r[k][c];
+            rod_fwd(r, q % 3, D);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) {
+                RGp[e] = s.RG[pa][e];
+                RGk[e] = s.RG[k][e];
+            }
+            mm(RGp, D, t1);
+            mmt(t1, RGk, Om);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) {
+                m.D[q][e] = D[e];
+                m.Om[q][e] = Om[e];
+            }
+        } else if (tid >= 192 && tid < 195) {
+            float r[3], D[9];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = s.rg[c];
+            rod_fwd(r, tid - 192, D);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) m.dRg[tid - 192][e] = D[e];
+        }
+        for (int w = tid; w < kMJ * kMBeta; w += kFThreads) {
+            const int i = w / kMBeta, bb = w % kMBeta;
+            float acc[3] = {0.f, 0.f, 0.f};
+            int c = i;
+            while (c > 0) {
+                const int pa = mano_parent(p.parents, c);
+                float RGp[9], d[3], f[3];
+#pragma unroll
+                for (int e = 0; e < 9; ++e) RGp[e] = s.RG[pa][e];
+#pragma unroll
+                for (int cc = 0; cc < 3; ++cc)
+                    d[cc] = p.joint_s[(c * 3 + cc) * kMBeta + bb] - p.joint_s[(pa * 3 + cc) * kMBeta + bb];
+                mv(RGp, d, f);
+#pragma unroll
+                for (int cc = 0; cc < 3; ++cc) acc[cc] += f[cc];
+                c = pa;
+            }
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) m.dtb[i][bb][cc] = acc[cc] + p.joint_s[cc * kMBeta + bb];
+        }
+    }
+    __syncthreads();
+    float Rg[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Rg[e] = s.Rg[e];
+    if (tid < kFJoints) {
+        const int jm = m.map[tid];
+        float d[3], v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = m.y[jm][c];
+        mv(Rg, d, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m.x[3 * tid + c] = v[c];
+    }
+    if (want_jac) {
+        for (int w = tid; w < kFJoints * kFModel; w += kFThreads) {
+            const int j = w / kFModel, q = w % kFModel, jm = m.map[j];
+            float v[3];
+            if (q < 3) {
+                float D[9], d[3];
+#pragma unroll
+                for (int e = 0; e < 9; ++e) D[e] = m.dRg[q][e];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) d[c] = m.y[jm][c];
+                mv(D, d, v);
+            } else {
+                float dy[3], d1[3];
+                if (q < 3 + kFPose) {
+                    const int q2 = q - 3, k = 1 + q2 / 3;
+                    jac_pose_col(m, jm, q2, k, dy);
+                    jac_pose_col(m, 1, q2, k, d1);
+                } else {
+                    jac_beta_col(m, p, jm, q - 3 - kFPose, dy);
+                    jac_beta_col(m, p, 1, q - 3 - kFPose, d1);
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) dy[c] -= d1[c];
+                mv(Rg, dy, v);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) J[(3 * j + c) * ld + q] = scale * v[c];
+        }
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ bool fit_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// init = 1, one thread: rots, trans, log_scale of the weighted similarity that takes the model joints x onto the targets y
+__device__ void fit_procrustes(const float* x, const float* y, const float* w, float* p) {
+    double W = 0.0, mx[3] = {0, 0, 0}, my[3] = {0, 0, 0};
+    for (int j = 0; j < kFJoints; ++j) {
+        W += w[j];
+        for (int c = 0; c < 3; ++c) {
+            mx[c] += (double)w[j] * x[3 * j + c];
+            my[c] += (double)w[j] * y[3 * j + c];
+        }
+    }
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, sc = 1.0;
+    if (W > 0.0) {
+        for (int c = 0; c < 3; ++c) {
+            mx[c] /= W;
+            my[c] /= W;
+        }
+        double K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, var = 0.0;
+        for (int j = 0; j < kFJoints; ++j)
+            for (int a = 0; a < 3; ++a) {
+                const double xa = x[3 * j + a] - mx[a];
+                var += w[j] * xa * xa;
+                for (int c = 0; c < 3; ++c) K[3 * a + c] += w[j] * xa * (y[3 * j + c] - my[c]);
+            }
+        horn_rotation(K, R);   // maximises sum_j y_j . R x_j
+        double num = 0.0;
+        for (int c = 0; c < 3; ++c)
+            for (int a = 0; a < 3; ++a) num += R[3 * c + a] * K[3 * a + c];
+        sc = num / var;
+        if (!(sc > 1e-30 && sc < 1e30)) sc = 1.0;   // a degenerate point set: keep the model's size
+    } else {
+        for (int c = 0; c < 3; ++c) mx[c] = my[c] = 0.0;
+    }
+    // R -> unit quaternion by the largest of the four candidates, w >= 0, then r = 2 atan2(|v|, w) v / |v|
+    double qw, qx, qy, qz;
+    const double tr = R[0] + R[4] + R[8];
+    if (tr > 0.0) {
+        const double S = 2.0 * sqrt(tr + 1.0);
+        qw = 0.25 * S, qx = (R[7] - R[5]) / S, qy = (R[2] - R[6]) / S, qz = (R[3] - R[1]) / S;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double S = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
+        qw = (R[7] - R[5]) / S, qx = 0.25 * S, qy = (R[1] + R[3]) / S, qz = (R[2] + R[6]) / S;
+    } else if (R[4] > R[8]) {
+        const double S = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
+        qw = (R[2] - R[6]) / S, qx = (R[1] + R[3]) / S, qy = 0.25 * S, qz = (R[5] + R[7]) / S;
+    } else {
+        const double S = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
+        qw = (R[3] - R[1]) / S, qx = (R[2] + R[6]) / S, qy = (R[5] + R[7]) / S, qz = 0.25 * S;
+    }
+    if (qw < 0.0) qw = -qw, qx = -qx, qy = -qy, qz = -qz;
+    const double n = sqrt(qx * qx + qy * qy + qz * qz);
+    const double k = n > 1e-12 ? 2.0 * atan2(n, qw) / n : 2.0;
+    p[0] = (float)(k * qx);
+    p[1] = (float)(k * qy);
+    p[2] = (float)(k * qz);
+    for (int c = 0; c < 3; ++c)
+        p[kFModel + c] = (float)(my[c] - sc * (R[3 * c] * mx[0] + R[3 * c + 1] * mx[1] + R[3 * c + 2] * mx[2]));
+    p[kFU - 1] = (float)log(sc);
+}
+
+}  // namespace scat

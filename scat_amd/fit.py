@@ -7,6 +7,12 @@ which predict [B,66] (camera + 21 joints), to ManoLayer and MeshRenderer, which 
     verts = fitter.mesh(res)                           # [B,V,3] in the frame of the predicted joints
     frames = renderer.render(verts, out66[:, :3])      # with the predicted camera
 
+fit_keypoints (include/scat_mano_fit_kp.h, csrc/mano_fit_kp.hip) takes 2-D keypoints in pixels, 3-D joints or both, with a
+Geman-McClure loss and joint limits, and solves for the weak-perspective camera as well:
+
+    res = fitter.fit_keypoints(joints2d=kp2d, sigma2=10.0)     # KeypointFitResult(..., cam, cost, accepted, p)
+    frames = renderer.render(fitter.mesh(res), res.cam)        # lands on the keypoints
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -21,6 +27,7 @@ from .ops import _p, _stream
 UNKNOWNS = 62                  # rots 3, poses 45, betas 10, trans 3, log_scale 1: SCAT_FIT_UNKNOWNS
 MAX_ITERS = 64                 # SCAT_FIT_MAX_ITERS
 ALL_FREE = (1 << UNKNOWNS) - 1
+KP_UNKNOWNS = 65               # the 62, then the camera cs, ctx, cty: SCAT_FIT_KP_UNKNOWNS
 SLICES = {"rots": slice(0, 3), "poses": slice(3, 48), "betas": slice(48, 58), "trans": slice(58, 61), "log_scale": slice(61, 62)}
 
 
@@ -43,6 +50,18 @@ class FitResult(NamedTuple):
     cost: torch.Tensor       # [B], +inf for a sample whose targets were not finite
     accepted: torch.Tensor   # [B] int32
     p: torch.Tensor          # [B,62]: the five groups as the kernel holds them (log_scale last)
+
+
+class KeypointFitResult(NamedTuple):
+    rots: torch.Tensor       # [B,3]
+    poses: torch.Tensor      # [B,45]
+    betas: torch.Tensor      # [B,10]
+    trans: torch.Tensor      # [B,3]
+    scale: torch.Tensor      # [B]
+    cam: torch.Tensor        # [B,3]: (s, tx, ty), the camera of project_outputs and MeshRenderer.render
+    cost: torch.Tensor       # [B], +inf for a sample whose targets were not finite
+    accepted: torch.Tensor   # [B] int32
+    p: torch.Tensor          # [B,65]: the six groups as the kernel holds them (log_scale, then the camera, last)
 
 
 def _check_model(what, model, ref):
@@ -77,6 +96,21 @@ def mano_fit(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose
     lib().scat_mano_fit(*_model_args(model), _p(targets), _p(weights), _p(joint_map), _p(p), _p(cost), _p(accepted), B, model.V,
                         model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose), float(w_beta),
                         int(free), _stream())
+    return cost, accepted
+
+
+def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
+                w_beta, w_limit, sigma3, sigma2, half_w, half_h, free=ALL_FREE, free_cam=7):
+    """scat_mano_fit_kp as it is declared: targets3 [B,21,3] / weights3 [B,21], targets2 [B,21,2] / weights2 [B,21] (None
+    leaves a term out, or means all ones), joint_map int32 [21] on the device, pose_lo / pose_hi [45] or None, p [B,65]
+    (read when init = 0, written) -> (cost [B], accepted [B] int32)"""
+    B = p.shape[0]
+    cost = torch.empty((B,), dtype=torch.float32, device=p.device)
+    accepted = torch.empty((B,), dtype=torch.int32, device=p.device)
+    lib().scat_mano_fit_kp(*_model_args(model), _p(targets3), _p(weights3), _p(targets2), _p(weights2), _p(joint_map), _p(pose_lo),
+                           _p(pose_hi), _p(p), _p(cost), _p(accepted), B, model.V, model.parents_packed, *model.tips, int(iters),
+                           int(init), float(lambda0), float(w_pose), float(w_beta), float(w_limit), float(sigma3), float(sigma2),
+                           float(half_w), float(half_h), int(free), int(free_cam), _stream())
     return cost, accepted
 
 
@@ -140,6 +174,72 @@ class ManoFitter:
         if out66.dim() != 2 or out66.shape[1] != 66:
             raise ScatError(f"fit_outputs needs the network's output [B,66], got {tuple(out66.shape)}")
         return self.fit(out66.detach()[:, 3:].reshape(-1, 21, 3).contiguous(), weights)
+
+    def fit_keypoints(self, joints3d=None, joints2d=None, w3=None, w2=None, size=(224, 224), sigma3=0.0, sigma2=0.0, limits=None,
+                      w_limit=0.0, init=None, free=None, free_cam=7, iters=None):
+        """joints3d [B,21,3] and / or joints2d [B,21,2] (pixels of a frame of size = (H, W)) -> KeypointFitResult.
+        w3, w2: [B,21] or None (all ones).  UNITS: the 3-D term is in the joints' unit squared and the 2-D term in pixels
+        squared, and w2 balances them: with joints in metres, w2 = 1e-6 makes a pixel count like a millimetre.
+        sigma3, sigma2: the Geman-McClure scales in the joints' unit and in pixels, 0 for the quadratic loss.
+        limits: (lo[45], hi[45]) on poses with the weight w_limit; an entry that is not finite is no limit.
+        init: None for the closed-form start, or p [B,65] / a KeypointFitResult (it is not modified).
+        free: bit i clear freezes unknown i < 62; None frees everything, or everything but trans and log_scale when
+        joints3d is None (they are a gauge of the camera then).  free_cam: bits 0, 1, 2 free cs, ctx, cty; without
+        joints2d the camera has no rows and stays frozen.  A sample with a target or weight that is not finite, or a
+        negative weight, is not fitted: cost +inf, accepted 0, p its start."""
+        what = "ManoFitter.fit_keypoints"
+        if joints3d is None and joints2d is None:
+            raise ScatError(f"{what} needs joints3d, joints2d or both")
+        given = [t for t in (joints3d, joints2d, w3, w2) if t is not None]
+        _need_gpu(what, *given)
+        ref = joints3d if joints3d is not None else joints2d
+        _check_model(what, self.model, ref)
+        B = ref.shape[0]
+        for name, t, shape in (("joints3d", joints3d, (B, 21, 3)), ("joints2d", joints2d, (B, 21, 2)), ("w3", w3, (B, 21)),
+                               ("w2", w2, (B, 21))):
+            if t is not None and (B == 0 or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != ref.device):
+                raise ScatError(f"{what} needs fp32 {name} {list(shape)} with B >= 1 on {ref.device}, got {t.dtype} "
+                                f"{tuple(t.shape)} on {t.device}")
+        if (w3 is not None and joints3d is None) or (w2 is not None and joints2d is None):
+            raise ScatError(f"{what}: weights given without their joints")
+        lo = hi = None
+        if limits is not None:
+            lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(ref.device).contiguous() for t in limits)
+            if tuple(lo.shape) != (POSE,) or tuple(hi.shape) != (POSE,):
+                raise ScatError(f"{what} needs limits (lo[45], hi[45]), got {tuple(lo.shape)}, {tuple(hi.shape)}")
+        H, W = (float(v) for v in size)
+        if not (H > 0 and W > 0):
+            raise ScatError(f"{what}: size {size} must be positive")
+        if init is None:
+            p = torch.empty((B, KP_UNKNOWNS), dtype=torch.float32, device=ref.device)
+        else:
+            p0 = init.p if isinstance(init, KeypointFitResult) else init
+            _need_gpu(what, p0)
+            if tuple(p0.shape) != (B, KP_UNKNOWNS) or p0.dtype != torch.float32:
+                raise ScatError(f"{what} needs an fp32 start [{B},{KP_UNKNOWNS}], got {p0.dtype} {tuple(p0.shape)}")
+            p = p0.clone().contiguous()
+        iters = self.iters if iters is None else int(iters)
+        if not 1 <= iters <= MAX_ITERS:
+            raise ScatError(f"{what}: {iters} iterations outside 1..{MAX_ITERS}")
+        if free is None:
+            free = ALL_FREE if joints3d is not None else free_mask(trans=False, log_scale=False)
+        if not 0 <= int(free) <= ALL_FREE or not 0 <= int(free_cam) <= 7:
+            raise ScatError(f"{what}: free has bits above {UNKNOWNS - 1} set, or free_cam is outside 0..7")
+        if min(float(sigma3), float(sigma2), float(w_limit)) < 0:
+            raise ScatError(f"{what}: sigma3, sigma2 and w_limit must not be negative")
+        c = lambda t: None if t is None else t.contiguous()
+        cost, accepted = mano_fit_kp(self.model, c(joints3d), c(w3), c(joints2d), c(w2), self._map_on(ref.device), lo, hi, p, iters,
+                                     0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma3, sigma2,
+                                     0.5 * W, 0.5 * H, free, int(free_cam) if joints2d is not None else 0)
+        return KeypointFitResult(p[:, 0:3], p[:, 3:48], p[:, 48:58], p[:, 58:61], torch.exp(p[:, 61]), p[:, 62:65], cost, accepted, p)
+
+    def project(self, result, size=(224, 224)):
+        """the fitted joints of a KeypointFitResult through its camera -> [B,21,2] pixels of a frame of size = (H, W):
+        project_outputs on (result.cam, joints(result))"""
+        from .render import project_outputs
+
+        j = self.joints(result)
+        return project_outputs(torch.cat([result.cam, j.reshape(j.shape[0], 63)], dim=1), int(size[0]), int(size[1]))
 
     def joints(self, result):
         """the fitted joints [B,21,3] in the targets' frame and order"""
