@@ -11,8 +11,8 @@
 //   beta b        d t_i = d J_0 + sum over the path of RG_parent (dJ_c - dJ_parent), a tip
 //                 sum_i w_i (RG_i (shapedirs_b - dJ_i) + d t_i)
 // mano_fit_kernel keeps J (63 x 62), the normal matrix with g as its 63rd row, and both parameter vectors in LDS.  The
-// factorisation is a left-looking Cholesky, one thread per row, two barriers per column; carrying g as an extra row
-// gives L^-1 g for free, and the back substitution is column-oriented.  All sums are sequential loops in a fixed order.
+// factorisation, the back substitution, the accept step and the final write are mano_fit_common.h's lm_solve, lm_accept,
+// lm_commit and lm_write, described there.  All sums are sequential loops in a fixed order.
 #include "mano_fit_common.h"
 
 namespace scat {
@@ -104,12 +104,8 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_kernel(FitArgs a) {
         f.cost = INFINITY;
     }
     __syncthreads();
-    if (f.bad) {   // the same for every thread of the workgroup
-        if (a.init && tid < kFU) a.p[b * kFU + tid] = 0.f;
-        if (tid == 0) {
-            a.cost[b] = INFINITY;
-            a.accepted[b] = 0;
-        }
+    if (f.bad) {   // the same for every thread of the workgroup; acc and cost are as lm_write wants them
+        lm_write<kFU>(f, a, b);
         return;
     }
     ManoArgs pc = a.m, pt = a.m;
@@ -150,56 +146,15 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_kernel(FitArgs a) {
             }
         }
         __syncthreads();
-        // left-looking Cholesky, row tid; row 62 (g) rides along and ends as L^-1 g
-        for (int k = 0; k < kFU; ++k) {
-            if (tid >= k && tid <= kFU) {
-                float s = f.A[tid][k];
-                for (int j = 0; j < k; ++j) s -= f.A[tid][j] * f.A[k][j];
-                f.col[tid] = s;
-            }
-            __syncthreads();
-            const float d = f.col[k];
-            if (!(d > 0.f) || !fit_finite(d)) {
-                if (tid == 0) f.fail = 1;
-            }
-            const float l = sqrtf(d);
-            if (tid == k) f.A[k][k] = l;
-            else if (tid > k && tid <= kFU) f.A[tid][k] = f.col[tid] / l;
-            __syncthreads();
-        }
-        // L^T x = L^-1 g by columns, last first; delta = -x
-        for (int k = kFU - 1; k >= 0; --k) {
-            const float xk = f.A[kFU][k] / f.A[k][k];
-            if (tid < k) f.A[kFU][tid] -= f.A[k][tid] * xk;
-            else if (tid == k) f.delta[k] = -xk;
-            __syncthreads();
-        }
+        lm_solve<kFU>(f);
         if (tid < kFU) f.pt[tid] = ((fm >> tid) & 1u) ? f.p[tid] + f.delta[tid] : f.p[tid];
         jac_eval(m, pt, 0, false, 1.f, nullptr, 0);
         fit_residual(m, f, f.pt, false);
         __syncthreads();
-        if (tid == 0) {
-            const float ct = fit_cost(f, f.pt, a.w_pose, a.w_beta);
-            bool ok = !f.fail && ct < f.cost;
-            for (int i = 0; i < kFU; ++i) ok = ok && fit_finite(f.pt[i]);
-            f.take = ok;
-            if (ok) {
-                f.cost = ct;
-                f.acc += 1;
-                f.lambda = fmaxf(f.lambda * 0.1f, kFLambdaMin);
-            } else {
-                f.lambda = fminf(f.lambda * 10.f, kFLambdaMax);
-            }
-        }
-        __syncthreads();
-        if (f.take && tid < kFU) f.p[tid] = f.pt[tid];
-        __syncthreads();
+        if (tid == 0) lm_accept<kFU>(f, fit_cost(f, f.pt, a.w_pose, a.w_beta));
+        lm_commit<kFU>(f);
     }
-    if ((a.init || f.acc > 0) && tid < kFU) a.p[b * kFU + tid] = f.p[tid];
-    if (tid == 0) {
-        a.cost[b] = fit_finite(f.cost) ? f.cost : INFINITY;   // also NaN: a start that is not finite
-        a.accepted[b] = f.acc;
-    }
+    lm_write<kFU>(f, a, b);
 }
 
 }  // namespace scat
@@ -229,18 +184,13 @@ extern "C" int scat_mano_fit(const float* blend, const float* joint_t, const flo
     const char* fn = "scat_mano_fit";
     const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, targets, joint_map, p, cost, accepted};
     const int tips[kMTips] = {tip0, tip1, tip2, tip3, tip4};
-    FitArgs a = {{blend, joint_t, joint_s, weights_t, hands_mean, nullptr, nullptr, nullptr, V, 0, parents, {{tip0, tip1, tip2, tip3, tip4}}},
+    FitArgs a = {fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, tips),
                  targets, weights, joint_map, p, cost, accepted, iters, init, lambda0, w_pose, w_beta, free_mask};
-    const int rc = mano_validate(fn, ptrs, 10, B, V, parents, tips, &a.m.levels);
+    int rc = mano_validate(fn, ptrs, 10, B, V, parents, tips, &a.m.levels);
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(((uintptr_t)weights & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
-    SCAT_REQUIRE(iters >= 1 && iters <= SCAT_FIT_MAX_ITERS, SCAT_E_ARG, "%s: %d iterations outside 1..%d", fn, iters,
-                 SCAT_FIT_MAX_ITERS);
-    SCAT_REQUIRE(init == 0 || init == 1, SCAT_E_ARG, "%s: init %d must be 0 (p is the start) or 1 (Procrustes)", fn, init);
-    SCAT_REQUIRE(lambda0 > 0.f && lambda0 <= kFLambdaMax, SCAT_E_ARG, "%s: lambda0 %g outside (0, %g]", fn, (double)lambda0,
-                 (double)kFLambdaMax);
-    SCAT_REQUIRE(w_pose >= 0.f && w_pose < INFINITY, SCAT_E_ARG, "%s: w_pose %g must be finite and not negative", fn, (double)w_pose);
-    SCAT_REQUIRE(w_beta >= 0.f && w_beta < INFINITY, SCAT_E_ARG, "%s: w_beta %g must be finite and not negative", fn, (double)w_beta);
+    rc = fit_check_args(fn, "Procrustes", iters, init, lambda0, w_pose, w_beta);
+    if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
     hipLaunchKernelGGL(mano_fit_kernel, dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
     SCAT_LAUNCH_CHECK(fn);

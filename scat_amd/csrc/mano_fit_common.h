@@ -1,6 +1,9 @@
 // What the two fit kernels share (mano_fit.hip: 3-D joints, quadratic; mano_fit_kp.hip: 2-D keypoints, robust loss, joint
-// limits): the constants, the LDS state of the joints' Jacobian with jac_load_model and jac_eval, the Procrustes start and
-// fit_finite.  mano_fit.hip's header comment has the derivation of the Jacobian's columns.
+// limits): the constants, the LDS state of the joints' Jacobian with jac_load_model and jac_eval, the Procrustes start with
+// fit_axis_angle, fit_finite, the steps of the solver that do not depend on the problem (lm_solve, lm_accept, lm_commit,
+// lm_write) and the entry points' shared argument handling.  mano_fit.hip's header comment has the derivation of the
+// Jacobian's columns.  What stays in each kernel is what its problem decides: staging, the usable-inputs test, the start,
+// residuals and cost, and the walk that assembles the normal equations, whose row sums compile well only in the kernel.
 #pragma once
 #include "mano_common.h"
 
@@ -282,6 +285,30 @@ __device__ void jac_eval(JacLds& m, const ManoArgs& p, int64_t b, bool want_jac,
 
 __device__ __forceinline__ bool fit_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
+// The rotation matrix R as an axis-angle r: R -> unit quaternion by the largest of the four candidates, w >= 0, then
+// r = 2 atan2(|v|, w) v / |v|
+__device__ void fit_axis_angle(const double* R, float* r) {
+    double qw, qx, qy, qz;
+    const double tr = R[0] + R[4] + R[8];
+    if (tr > 0.0) {
+        const double S = 2.0 * sqrt(tr + 1.0);
+        qw = 0.25 * S, qx = (R[7] - R[5]) / S, qy = (R[2] - R[6]) / S, qz = (R[3] - R[1]) / S;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double S = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
+        qw = (R[7] - R[5]) / S, qx = 0.25 * S, qy = (R[1] + R[3]) / S, qz = (R[2] + R[6]) / S;
+    } else if (R[4] > R[8]) {
+        const double S = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
+        qw = (R[2] - R[6]) / S, qx = (R[1] + R[3]) / S, qy = 0.25 * S, qz = (R[5] + R[7]) / S;
+    } else {
+        const double S = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
+        qw = (R[3] - R[1]) / S, qx = (R[2] + R[6]) / S, qy = (R[5] + R[7]) / S, qz = 0.25 * S;
+    }
+    if (qw < 0.0) qw = -qw, qx = -qx, qy = -qy, qz = -qz;
+    const double n = sqrt(qx * qx + qy * qy + qz * qz);
+    const double k = n > 1e-12 ? 2.0 * atan2(n, qw) / n : 2.0;
+    r[0] = (float)(k * qx), r[1] = (float)(k * qy), r[2] = (float)(k * qz);
+}
+
 // init = 1, one thread: rots, trans, log_scale of the weighted similarity that takes the model joints x onto the targets y
 __device__ void fit_procrustes(const float* x, const float* y, const float* w, float* p) {
     double W = 0.0, mx[3] = {0, 0, 0}, my[3] = {0, 0, 0};
@@ -314,31 +341,97 @@ __device__ void fit_procrustes(const float* x, const float* y, const float* w, f
     } else {
         for (int c = 0; c < 3; ++c) mx[c] = my[c] = 0.0;
     }
-    // R -> unit quaternion by the largest of the four candidates, w >= 0, then r = 2 atan2(|v|, w) v / |v|
-    double qw, qx, qy, qz;
-    const double tr = R[0] + R[4] + R[8];
-    if (tr > 0.0) {
-        const double S = 2.0 * sqrt(tr + 1.0);
-        qw = 0.25 * S, qx = (R[7] - R[5]) / S, qy = (R[2] - R[6]) / S, qz = (R[3] - R[1]) / S;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double S = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
-        qw = (R[7] - R[5]) / S, qx = 0.25 * S, qy = (R[1] + R[3]) / S, qz = (R[2] + R[6]) / S;
-    } else if (R[4] > R[8]) {
-        const double S = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
-        qw = (R[2] - R[6]) / S, qx = (R[1] + R[3]) / S, qy = 0.25 * S, qz = (R[5] + R[7]) / S;
-    } else {
-        const double S = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
-        qw = (R[3] - R[1]) / S, qx = (R[2] + R[6]) / S, qy = (R[5] + R[7]) / S, qz = 0.25 * S;
-    }
-    if (qw < 0.0) qw = -qw, qx = -qx, qy = -qy, qz = -qz;
-    const double n = sqrt(qx * qx + qy * qy + qz * qz);
-    const double k = n > 1e-12 ? 2.0 * atan2(n, qw) / n : 2.0;
-    p[0] = (float)(k * qx);
-    p[1] = (float)(k * qy);
-    p[2] = (float)(k * qz);
+    fit_axis_angle(R, p);
     for (int c = 0; c < 3; ++c)
         p[kFModel + c] = (float)(my[c] - sc * (R[3 * c] * mx[0] + R[3 * c + 1] * mx[1] + R[3 * c + 2] * mx[2]));
     p[kFU - 1] = (float)log(sc);
 }
 
+// The steps of Levenberg-Marquardt that do not depend on the problem, on a kernel's LDS state f: A[N + 1][N] (lower
+// triangle: the damped normal matrix, g as row N), col[N + 1], delta, p, pt[N], cost, lambda, acc, fail, take.
+//
+// A left-looking Cholesky, one thread per row, two barriers per column; row N (g) rides along and ends as L^-1 g.  Then
+// L^T x = L^-1 g by columns, last first, one barrier per column; delta = -x.
+template <int N, class F>
+__device__ __forceinline__ void lm_solve(F& f) {
+    const int tid = threadIdx.x;
+    for (int k = 0; k < N; ++k) {
+        if (tid >= k && tid <= N) {
+            float s = f.A[tid][k];
+            for (int j = 0; j < k; ++j) s -= f.A[tid][j] * f.A[k][j];
+            f.col[tid] = s;
+        }
+        __syncthreads();
+        const float d = f.col[k];
+        if (!(d > 0.f) || !fit_finite(d)) {
+            if (tid == 0) f.fail = 1;
+        }
+        const float l = sqrtf(d);
+        if (tid == k) f.A[k][k] = l;
+        else if (tid > k && tid <= N) f.A[tid][k] = f.col[tid] / l;
+        __syncthreads();
+    }
+    for (int k = N - 1; k >= 0; --k) {
+        const float xk = f.A[N][k] / f.A[k][k];
+        if (tid < k) f.A[N][tid] -= f.A[k][tid] * xk;
+        else if (tid == k) f.delta[k] = -xk;
+        __syncthreads();
+    }
+}
+
+// One thread, ct the cost at pt: the step is taken if the pivots were positive, pt is finite and the cost drops
+template <int N, class F>
+__device__ __forceinline__ void lm_accept(F& f, float ct) {
+    bool ok = !f.fail && ct < f.cost;
+    for (int i = 0; i < N; ++i) ok = ok && fit_finite(f.pt[i]);
+    f.take = ok;
+    if (ok) {
+        f.cost = ct;
+        f.acc += 1;
+        f.lambda = fmaxf(f.lambda * 0.1f, kFLambdaMin);
+    } else {
+        f.lambda = fminf(f.lambda * 10.f, kFLambdaMax);
+    }
+}
+
+// All threads, after lm_accept
+template <int N, class F>
+__device__ __forceinline__ void lm_commit(F& f) {
+    __syncthreads();
+    if (f.take && threadIdx.x < N) f.p[threadIdx.x] = f.pt[threadIdx.x];
+    __syncthreads();
+}
+
+// The results of sample b.  A sample that was not fitted has acc = 0 and cost = +inf from the start: accepted 0, p its start
+template <int N, class F, class A>
+__device__ __forceinline__ void lm_write(const F& f, const A& a, int64_t b) {
+    const int tid = threadIdx.x;
+    if ((a.init || f.acc > 0) && tid < N) a.p[b * N + tid] = f.p[tid];
+    if (tid == 0) {
+        a.cost[b] = fit_finite(f.cost) ? f.cost : INFINITY;   // also NaN: a start that is not finite
+        a.accepted[b] = f.acc;
+    }
+}
+
 }  // namespace scat
+
+// The model's arguments of a fit's entry point; rots / poses / betas are set by the kernel (LDS), levels by mano_validate
+static scat::ManoArgs fit_model_args(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                     const float* hands_mean, int V, uint64_t parents, const int* tips) {
+    return {blend, joint_t, joint_s, weights_t, hands_mean, nullptr, nullptr, nullptr, V, 0, parents,
+            {{tips[0], tips[1], tips[2], tips[3], tips[4]}}};
+}
+
+// The checks that every fit's entry point makes at the same place (free_mask's comes later in scat_mano_fit_kp, and stays
+// there); start: what it calls its closed-form start
+static int fit_check_args(const char* fn, const char* start, int iters, int init, float lambda0, float w_pose, float w_beta) {
+    using namespace scat;
+    SCAT_REQUIRE(iters >= 1 && iters <= SCAT_FIT_MAX_ITERS, SCAT_E_ARG, "%s: %d iterations outside 1..%d", fn, iters,
+                 SCAT_FIT_MAX_ITERS);
+    SCAT_REQUIRE(init == 0 || init == 1, SCAT_E_ARG, "%s: init %d must be 0 (p is the start) or 1 (%s)", fn, init, start);
+    SCAT_REQUIRE(lambda0 > 0.f && lambda0 <= kFLambdaMax, SCAT_E_ARG, "%s: lambda0 %g outside (0, %g]", fn, (double)lambda0,
+                 (double)kFLambdaMax);
+    SCAT_REQUIRE(w_pose >= 0.f && w_pose < INFINITY, SCAT_E_ARG, "%s: w_pose %g must be finite and not negative", fn, (double)w_pose);
+    SCAT_REQUIRE(w_beta >= 0.f && w_beta < INFINITY, SCAT_E_ARG, "%s: w_beta %g must be finite and not negative", fn, (double)w_beta);
+    return SCAT_OK;
+}

@@ -1,7 +1,7 @@
 // The MANO fit to keypoints, include/scat_mano_fit_kp.h: mano_fit_kernel's Levenberg-Marquardt with a 2-D reprojection
 // term through a weak-perspective camera, Geman-McClure weights (IRLS) and joint limits.  One workgroup of 256 threads per
-// sample, all iterations in one launch, everything in LDS; jac_eval, the Procrustes start and the constants are
-// mano_fit_common.h's.
+// sample, all iterations in one launch, everything in LDS; jac_eval, the Procrustes start, the constants and the solver's
+// steps that do not depend on the problem (lm_solve, lm_accept, lm_commit, lm_write) are mano_fit_common.h's.
 //
 // 65 unknowns: scat_mano_fit's 62, then cs, ctx, cty.  The 42 rows of the 2-D term are not stored: in the first 62 columns
 // row (j, c) of the 2-D term is cs half_c times row 3 j + c of the 3-D Jacobian, and its three camera columns are
@@ -190,30 +190,6 @@ __device__ void kp_rodrigues(const double r[3], double R[9]) {
     R[6] = cb * x * z - ca * y, R[7] = cb * y * z + ca * x, R[8] = 1.0 + cb * (z * z - t);
 }
 
-// fit_procrustes' last step on its own: R -> unit quaternion by the largest of the four candidates, w >= 0, then
-// r = 2 atan2(|v|, w) v / |v|
-__device__ void kp_axis_angle(const double* R, float* r) {
-    double qw, qx, qy, qz;
-    const double tr = R[0] + R[4] + R[8];
-    if (tr > 0.0) {
-        const double S = 2.0 * sqrt(tr + 1.0);
-        qw = 0.25 * S, qx = (R[7] - R[5]) / S, qy = (R[2] - R[6]) / S, qz = (R[3] - R[1]) / S;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double S = 2.0 * sqrt(1.0 + R[0] - R[4] - R[8]);
-        qw = (R[7] - R[5]) / S, qx = 0.25 * S, qy = (R[1] + R[3]) / S, qz = (R[2] + R[6]) / S;
-    } else if (R[4] > R[8]) {
-        const double S = 2.0 * sqrt(1.0 + R[4] - R[0] - R[8]);
-        qw = (R[2] - R[6]) / S, qx = (R[1] + R[3]) / S, qy = 0.25 * S, qz = (R[5] + R[7]) / S;
-    } else {
-        const double S = 2.0 * sqrt(1.0 + R[8] - R[0] - R[4]);
-        qw = (R[3] - R[1]) / S, qx = (R[2] + R[6]) / S, qy = (R[5] + R[7]) / S, qz = 0.25 * S;
-    }
-    if (qw < 0.0) qw = -qw, qx = -qx, qy = -qy, qz = -qz;
-    const double n = sqrt(qx * qx + qy * qy + qz * qz);
-    const double k = n > 1e-12 ? 2.0 * atan2(n, qw) / n : 2.0;
-    r[0] = (float)(k * qx), r[1] = (float)(k * qy), r[2] = (float)(k * qz);
-}
-
 // init = 1 with a 3-D term, one thread, after fit_procrustes: the camera that takes m.xy at the start p onto the
 // normalised 2-D targets, one isotropic scale
 __device__ void kp_camera_start(const float* x, const KpLds& f, const KpArgs& a, float* p) {
@@ -296,7 +272,7 @@ __device__ void kp_start_2d(const float* x, const KpLds& f, const KpArgs& a, flo
     if (!(cs > 1e-30 && cs < 1e30)) return;   // a degenerate point set: p stays the identity
     const double phi = atan2(bz[1], bz[0]), c = cos(phi), s = sin(phi);
     const double R0[9] = {c, -s, 0, s, c, 0, 0, 0, 1}, R1[9] = {-c, -s, 0, -s, c, 0, 0, 0, -1};
-    kp_axis_angle(best ? R1 : R0, p);
+    fit_axis_angle(best ? R1 : R0, p);
     p[kKCam] = (float)cs;
     p[kKCam + 1] = (float)(bt[0] / cs);
     p[kKCam + 2] = (float)(bt[1] / cs);
@@ -340,12 +316,8 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_kp_kernel(KpArgs a) {
         f.cost = INFINITY;
     }
     __syncthreads();
-    if (f.bad) {   // the same for every thread of the workgroup
-        if (a.init && tid < kKU) a.p[b * kKU + tid] = f.p[tid];
-        if (tid == 0) {
-            a.cost[b] = INFINITY;
-            a.accepted[b] = 0;
-        }
+    if (f.bad) {   // the same for every thread of the workgroup; acc and cost are as lm_write wants them
+        lm_write<kKU>(f, a, b);
         return;
     }
     ManoArgs pc = a.m, pt = a.m;
@@ -395,56 +367,15 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_kp_kernel(KpArgs a) {
             }
         }
         __syncthreads();
-        // left-looking Cholesky, row tid; row 65 (g) rides along and ends as L^-1 g
-        for (int k = 0; k < kKU; ++k) {
-            if (tid >= k && tid <= kKU) {
-                float s = f.A[tid][k];
-                for (int j = 0; j < k; ++j) s -= f.A[tid][j] * f.A[k][j];
-                f.col[tid] = s;
-            }
-            __syncthreads();
-            const float d = f.col[k];
-            if (!(d > 0.f) || !fit_finite(d)) {
-                if (tid == 0) f.fail = 1;
-            }
-            const float l = sqrtf(d);
-            if (tid == k) f.A[k][k] = l;
-            else if (tid > k && tid <= kKU) f.A[tid][k] = f.col[tid] / l;
-            __syncthreads();
-        }
-        // L^T x = L^-1 g by columns, last first; delta = -x
-        for (int k = kKU - 1; k >= 0; --k) {
-            const float xk = f.A[kKU][k] / f.A[k][k];
-            if (tid < k) f.A[kKU][tid] -= f.A[k][tid] * xk;
-            else if (tid == k) f.delta[k] = -xk;
-            __syncthreads();
-        }
+        lm_solve<kKU>(f);
         if (tid < kKU) f.pt[tid] = kp_free(a, tid) ? f.p[tid] + f.delta[tid] : f.p[tid];
         jac_eval(m, pt, 0, false, 1.f, nullptr, 0);
         kp_residual(m, f, a, f.pt, false);
         __syncthreads();
-        if (tid == 0) {
-            const float ct = kp_cost(f, a, f.pt);
-            bool ok = !f.fail && ct < f.cost;
-            for (int i = 0; i < kKU; ++i) ok = ok && fit_finite(f.pt[i]);
-            f.take = ok;
-            if (ok) {
-                f.cost = ct;
-                f.acc += 1;
-                f.lambda = fmaxf(f.lambda * 0.1f, kFLambdaMin);
-            } else {
-                f.lambda = fminf(f.lambda * 10.f, kFLambdaMax);
-            }
-        }
-        __syncthreads();
-        if (f.take && tid < kKU) f.p[tid] = f.pt[tid];
-        __syncthreads();
+        if (tid == 0) lm_accept<kKU>(f, kp_cost(f, a, f.pt));
+        lm_commit<kKU>(f);
     }
-    if ((a.init || f.acc > 0) && tid < kKU) a.p[b * kKU + tid] = f.p[tid];
-    if (tid == 0) {
-        a.cost[b] = fit_finite(f.cost) ? f.cost : INFINITY;   // also NaN: a start that is not finite
-        a.accepted[b] = f.acc;
-    }
+    lm_write<kKU>(f, a, b);
 }
 
 }  // namespace scat
@@ -463,10 +394,10 @@ extern "C" int scat_mano_fit_kp(const float* blend, const float* joint_t, const 
     const char* fn = "scat_mano_fit_kp";
     const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, joint_map, p, cost, accepted};
     const int tips[kMTips] = {tip0, tip1, tip2, tip3, tip4};
-    KpArgs a = {{blend, joint_t, joint_s, weights_t, hands_mean, nullptr, nullptr, nullptr, V, 0, parents, {{tip0, tip1, tip2, tip3, tip4}}},
+    KpArgs a = {fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, tips),
                 targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, cost, accepted, iters, init, lambda0,
                 w_pose, w_beta, w_limit, sigma3, sigma2, {half_w, half_h}, free_mask, free_cam};
-    const int rc = mano_validate(fn, ptrs, 9, B, V, parents, tips, &a.m.levels);
+    int rc = mano_validate(fn, ptrs, 9, B, V, parents, tips, &a.m.levels);
     if (rc != SCAT_OK) return rc;
     const uintptr_t opt = (uintptr_t)targets3 | (uintptr_t)weights3 | (uintptr_t)targets2 | (uintptr_t)weights2 |
                           (uintptr_t)pose_lo | (uintptr_t)pose_hi;
@@ -475,13 +406,8 @@ extern "C" int scat_mano_fit_kp(const float* blend, const float* joint_t, const 
     SCAT_REQUIRE(targets3 || !weights3, SCAT_E_ARG, "%s: weights3 given without targets3", fn);
     SCAT_REQUIRE(targets2 || !weights2, SCAT_E_ARG, "%s: weights2 given without targets2", fn);
     SCAT_REQUIRE(!pose_lo == !pose_hi, SCAT_E_ARG, "%s: pose_lo and pose_hi must both be given or both be null", fn);
-    SCAT_REQUIRE(iters >= 1 && iters <= SCAT_FIT_MAX_ITERS, SCAT_E_ARG, "%s: %d iterations outside 1..%d", fn, iters,
-                 SCAT_FIT_MAX_ITERS);
-    SCAT_REQUIRE(init == 0 || init == 1, SCAT_E_ARG, "%s: init %d must be 0 (p is the start) or 1 (the closed-form start)", fn, init);
-    SCAT_REQUIRE(lambda0 > 0.f && lambda0 <= kFLambdaMax, SCAT_E_ARG, "%s: lambda0 %g outside (0, %g]", fn, (double)lambda0,
-                 (double)kFLambdaMax);
-    SCAT_REQUIRE(kp_weight_ok(w_pose), SCAT_E_ARG, "%s: w_pose %g must be finite and not negative", fn, (double)w_pose);
-    SCAT_REQUIRE(kp_weight_ok(w_beta), SCAT_E_ARG, "%s: w_beta %g must be finite and not negative", fn, (double)w_beta);
+    rc = fit_check_args(fn, "the closed-form start", iters, init, lambda0, w_pose, w_beta);
+    if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(kp_weight_ok(w_limit), SCAT_E_ARG, "%s: w_limit %g must be finite and not negative", fn, (double)w_limit);
     SCAT_REQUIRE(kp_weight_ok(sigma3), SCAT_E_ARG, "%s: sigma3 %g must be finite and not negative", fn, (double)sigma3);
     SCAT_REQUIRE(kp_weight_ok(sigma2), SCAT_E_ARG, "%s: sigma2 %g must be finite and not negative", fn, (double)sigma2);

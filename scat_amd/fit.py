@@ -69,6 +69,29 @@ def _check_model(what, model, ref):
         raise ScatError(f"{what}: the model is on {model.device}, the inputs on {ref.device}: call ManoModel.to first")
 
 
+def _start(what, init, result_type, B, unknowns, device):
+    """the p [B,unknowns] a kernel reads and writes: empty for init None, else a checked copy of init (tensor or result)"""
+    if init is None:
+        return torch.empty((B, unknowns), dtype=torch.float32, device=device)
+    p0 = init.p if isinstance(init, result_type) else init
+    _need_gpu(what, p0)
+    if tuple(p0.shape) != (B, unknowns) or p0.dtype != torch.float32:
+        raise ScatError(f"{what} needs an fp32 start [{B},{unknowns}], got {p0.dtype} {tuple(p0.shape)}")
+    return p0.clone().contiguous()
+
+
+def _check_ranges(what, iters, masks_ok, and_cam=""):
+    if not 1 <= iters <= MAX_ITERS:
+        raise ScatError(f"{what}: {iters} iterations outside 1..{MAX_ITERS}")
+    if not masks_ok:
+        raise ScatError(f"{what}: free has bits above {UNKNOWNS - 1} set{and_cam}")
+
+
+def _groups(p):
+    """rots, poses, betas, trans, scale: the five groups every fit's p begins with"""
+    return p[:, 0:3], p[:, 3:48], p[:, 48:58], p[:, 58:61], torch.exp(p[:, 61])
+
+
 def mano_joints_jac(model, rots, poses, betas):
     """-> (joints [B,21,3], jac [B,63,58]): the 21 joints of mano_fwd and d joints / d (rots, poses, betas), one launch"""
     _need_gpu("mano_joints_jac", rots, poses, betas)
@@ -144,23 +167,13 @@ class ManoFitter:
             raise ScatError(f"ManoFitter.fit needs fp32 joints [B,21,3] with B >= 1, got {joints.dtype} {tuple(joints.shape)}")
         if weights is not None and (tuple(weights.shape) != (B, 21) or weights.dtype != torch.float32):
             raise ScatError(f"ManoFitter.fit needs fp32 weights [{B},21], got {weights.dtype} {tuple(weights.shape)}")
-        if init is None:
-            p = torch.empty((B, UNKNOWNS), dtype=torch.float32, device=joints.device)
-        else:
-            p0 = init.p if isinstance(init, FitResult) else init
-            _need_gpu("ManoFitter.fit", p0)
-            if tuple(p0.shape) != (B, UNKNOWNS) or p0.dtype != torch.float32:
-                raise ScatError(f"ManoFitter.fit needs an fp32 start [{B},{UNKNOWNS}], got {p0.dtype} {tuple(p0.shape)}")
-            p = p0.clone().contiguous()
+        p = _start("ManoFitter.fit", init, FitResult, B, UNKNOWNS, joints.device)
         iters = self.iters if iters is None else int(iters)
-        if not 1 <= iters <= MAX_ITERS:
-            raise ScatError(f"ManoFitter.fit: {iters} iterations outside 1..{MAX_ITERS}")
-        if not 0 <= int(free) <= ALL_FREE:
-            raise ScatError(f"ManoFitter.fit: free has bits above {UNKNOWNS - 1} set")
+        _check_ranges("ManoFitter.fit", iters, 0 <= int(free) <= ALL_FREE)
         cost, accepted = mano_fit(self.model, joints.contiguous(), None if weights is None else weights.contiguous(),
                                   self._map_on(joints.device), p, iters, 0 if init is not None else 1,
                                   self.lambda0, self.w_pose, self.w_beta, free)
-        return FitResult(p[:, 0:3], p[:, 3:48], p[:, 48:58], p[:, 58:61], torch.exp(p[:, 61]), cost, accepted, p)
+        return FitResult(*_groups(p), cost, accepted, p)
 
     def _map_on(self, device):
         if self.joint_map_d is None or self.joint_map_d.device != device:
@@ -210,28 +223,18 @@ class ManoFitter:
         H, W = (float(v) for v in size)
         if not (H > 0 and W > 0):
             raise ScatError(f"{what}: size {size} must be positive")
-        if init is None:
-            p = torch.empty((B, KP_UNKNOWNS), dtype=torch.float32, device=ref.device)
-        else:
-            p0 = init.p if isinstance(init, KeypointFitResult) else init
-            _need_gpu(what, p0)
-            if tuple(p0.shape) != (B, KP_UNKNOWNS) or p0.dtype != torch.float32:
-                raise ScatError(f"{what} needs an fp32 start [{B},{KP_UNKNOWNS}], got {p0.dtype} {tuple(p0.shape)}")
-            p = p0.clone().contiguous()
+        p = _start(what, init, KeypointFitResult, B, KP_UNKNOWNS, ref.device)
         iters = self.iters if iters is None else int(iters)
-        if not 1 <= iters <= MAX_ITERS:
-            raise ScatError(f"{what}: {iters} iterations outside 1..{MAX_ITERS}")
         if free is None:
             free = ALL_FREE if joints3d is not None else free_mask(trans=False, log_scale=False)
-        if not 0 <= int(free) <= ALL_FREE or not 0 <= int(free_cam) <= 7:
-            raise ScatError(f"{what}: free has bits above {UNKNOWNS - 1} set, or free_cam is outside 0..7")
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE and 0 <= int(free_cam) <= 7, ", or free_cam is outside 0..7")
         if min(float(sigma3), float(sigma2), float(w_limit)) < 0:
             raise ScatError(f"{what}: sigma3, sigma2 and w_limit must not be negative")
         c = lambda t: None if t is None else t.contiguous()
         cost, accepted = mano_fit_kp(self.model, c(joints3d), c(w3), c(joints2d), c(w2), self._map_on(ref.device), lo, hi, p, iters,
                                      0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma3, sigma2,
                                      0.5 * W, 0.5 * H, free, int(free_cam) if joints2d is not None else 0)
-        return KeypointFitResult(p[:, 0:3], p[:, 3:48], p[:, 48:58], p[:, 58:61], torch.exp(p[:, 61]), p[:, 62:65], cost, accepted, p)
+        return KeypointFitResult(*_groups(p), p[:, 62:65], cost, accepted, p)
 
     def project(self, result, size=(224, 224)):
         """the fitted joints of a KeypointFitResult through its camera -> [B,21,2] pixels of a frame of size = (H, W):
