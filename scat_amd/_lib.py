@@ -1,5 +1,5 @@
 """ctypes binding of libscat_hip.so. Prototypes are parsed from the public headers (HEADERS below): include/scat_hip.h
-(the train step), scat_eval.h (on-device evaluation), scat_mano_fit_kp.h (the MANO fit to 2-D and 3-D keypoints),
+(the train step), scat_mesh_eval.h (on-device mesh scoring), scat_eval.h (on-device evaluation), scat_mano_fit_kp.h (the MANO fit to 2-D and 3-D keypoints),
 scat_mano_fit.h (the MANO fit), scat_render.h (the mesh and skeleton renderer) and scat_mano.h (the MANO layer), so the
 headers are the single source of truth for the C ABI. The product path has NO fallback: if the library is missing, importing a kernel raises."""
 from __future__ import annotations
@@ -11,11 +11,12 @@ import re
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "include", "scat_hip.h")
 EVAL_HEADER = os.path.join(HERE, "..", "include", "scat_eval.h")
+MESH_EVAL_HEADER = os.path.join(HERE, "..", "include", "scat_mesh_eval.h")
 RENDER_HEADER = os.path.join(HERE, "..", "include", "scat_render.h")
 MANO_HEADER = os.path.join(HERE, "..", "include", "scat_mano.h")
 FIT_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit.h")
 FIT_KP_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_kp.h")
-HEADERS = (HEADER, EVAL_HEADER, FIT_KP_HEADER, FIT_HEADER, RENDER_HEADER, MANO_HEADER)   # every public header of the one library; parse_header() defaults to the first
+HEADERS = (HEADER, MESH_EVAL_HEADER, EVAL_HEADER, FIT_KP_HEADER, FIT_HEADER, RENDER_HEADER, MANO_HEADER)   # every public header of the one library; parse_header() defaults to the first
 LIBPATH = os.path.join(HERE, "libscat_hip.so")
 if os.environ.get("SCAT_LIBPATH"):
     # measurement tools only (tools/pw_stamp.py, rows_stamp.py): the -DSCAT_DIAG build whose kernels can overwrite their

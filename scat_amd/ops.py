@@ -1072,7 +1072,52 @@ def eval_accumulate(out, labels, thresholds, keep=None, record=None, want_per_sa
     return record, per_sample, aligned
 
 
-RENDER_PROJ_WORDS = 8   # 32-bit words per projected vertex (layout: include/scat_render.h scat_render_project)
+MESH_EVAL_RECORD_HEAD = 8   # doubles in front of the counts of a record row (layout: include/scat_mesh_eval.h)
+MESH_EVAL_SAMPLE_HEAD = 4   # doubles in front of the counts of a per_sample row
+
+
+def _mesh_thresholds(what, th, device, most):
+    if not isinstance(th, torch.Tensor):
+        th = torch.as_tensor([float(t) for t in th], dtype=torch.float32).to(device)
+    if not (th.is_cuda and th.dtype == torch.float32 and th.is_contiguous() and th.dim() == 1 and 1 <= th.numel() <= most):
+        raise ScatError(f"mesh_eval_accumulate needs {what} as a contiguous fp32 GPU vector of 1..{most} values "
+                        "(no CPU fallback on the product path)")
+    return th
+
+
+def mesh_eval_accumulate(pred, gt, thresholds, f_thresholds=(5.0, 15.0), keep=None, record=None, want_aligned=False):
+    """Mesh scores of one batch (include/scat_mesh_eval.h scat_mesh_eval_accumulate).  pred, gt [B,V,3] fp32 in metres,
+    vertex i of one corresponding to vertex i of the other, V <= 1024; thresholds (the vertex PCK curve, at most 128) and
+    f_thresholds (the F-score thresholds, at most 8): fp32 GPU vectors in mm, or sequences; keep: uint8 [B] or None;
+    record: an fp64 GPU row [8 + 2T + 2F] to write (a row of a caller's table) or None for a new one.
+    -> (record, per_sample [B, 4 + 2T + 6F] fp64, aligned [B,V,3] fp32 | None)."""
+    if not (isinstance(pred, torch.Tensor) and isinstance(gt, torch.Tensor) and pred.is_cuda and gt.is_cuda):
+        raise ScatError("mesh_eval_accumulate needs GPU tensors (no CPU fallback on the product path)")
+    _chk(pred, gt)
+    if pred.dim() != 3 or pred.shape[2] != 3 or pred.shape[0] == 0 or not 1 <= pred.shape[1] <= 1024:
+        raise ScatError(f"mesh_eval_accumulate needs predicted vertices [B,V,3] with 1 <= V <= 1024, got {tuple(pred.shape)}")
+    if gt.shape != pred.shape:
+        raise ScatError(f"mesh_eval_accumulate needs gt of pred's shape {tuple(pred.shape)}, got {tuple(gt.shape)}")
+    B, V = pred.shape[0], pred.shape[1]
+    thresholds = _mesh_thresholds("thresholds", thresholds, pred.device, 128)
+    f_thresholds = _mesh_thresholds("f_thresholds", f_thresholds, pred.device, 8)
+    T, F = thresholds.numel(), f_thresholds.numel()
+    if keep is not None and not (keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous()
+                                 and tuple(keep.shape) == (B,)):
+        raise ScatError(f"mesh_eval_accumulate needs keep as a contiguous uint8 GPU vector [{B}]")
+    n_rec = MESH_EVAL_RECORD_HEAD + 2 * T + 2 * F
+    if record is None:
+        record = torch.empty((n_rec,), dtype=torch.float64, device=pred.device)
+    elif not (record.is_cuda and record.dtype == torch.float64 and record.is_contiguous() and tuple(record.shape) == (n_rec,)):
+        raise ScatError(f"mesh_eval_accumulate needs record as a contiguous fp64 GPU row [{n_rec}]")
+    per_sample = torch.empty((B, MESH_EVAL_SAMPLE_HEAD + 2 * T + 6 * F), dtype=torch.float64, device=pred.device)
+    aligned = torch.empty((B, V, 3), dtype=torch.float32, device=pred.device) if want_aligned else None
+    lib().scat_mesh_eval_accumulate(_p(pred), _p(gt), V, _p(keep), _p(thresholds), T, _p(f_thresholds), F, _p(record),
+                                    _p(per_sample), _p(aligned), B, _stream())
+    return record, per_sample, aligned
+
+
+RENDER_PROJ_WORDS = 8  # 32-bit words per projected vertex (layout: include/scat_render.h scat_render_project)
 
 
 def _render_chk(what, *specs):
