@@ -1,7 +1,8 @@
 """ctypes binding of libscat_hip.so. Prototypes are parsed from the public headers (HEADERS below): include/scat_hip.h
 (the train step), scat_mesh_eval.h (on-device mesh scoring), scat_eval.h (on-device evaluation), scat_mano_fit_kp.h (the MANO fit to 2-D and 3-D keypoints),
 scat_mano_fit.h (the MANO fit), scat_render.h (the mesh and skeleton renderer) and scat_mano.h (the MANO layer), so the
-headers are the single source of truth for the C ABI. The product path has NO fallback: if the library is missing, importing a kernel raises."""
+headers are the single source of truth for the C ABI. EXTENSION_HEADERS (scat_mano_fit_seq.h, the MANO fit to a track of
+frames) are bound the same way beside them. The product path has NO fallback: if the library is missing, importing a kernel raises."""
 from __future__ import annotations
 
 import ctypes
@@ -17,6 +18,10 @@ MANO_HEADER = os.path.join(HERE, "..", "include", "scat_mano.h")
 FIT_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit.h")
 FIT_KP_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_kp.h")
 HEADERS = (HEADER, MESH_EVAL_HEADER, EVAL_HEADER, FIT_KP_HEADER, FIT_HEADER, RENDER_HEADER, MANO_HEADER)   # every public header of the one library; parse_header() defaults to the first
+# Headers bound beside HEADERS, the same way (parsed prototypes, the checked wrapper, a missing symbol raises), into
+# _Lib.by_extension: include/scat_mano_fit_seq.h, the MANO fit to a track of frames
+FIT_SEQ_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_seq.h")
+EXTENSION_HEADERS = (FIT_SEQ_HEADER,)
 LIBPATH = os.path.join(HERE, "libscat_hip.so")
 if os.environ.get("SCAT_LIBPATH"):
     # measurement tools only (tools/pw_stamp.py, rows_stamp.py): the -DSCAT_DIAG build whose kernels can overwrite their
@@ -78,7 +83,9 @@ class _Lib:
         # table the workspace tests index (tests/test_eval.py pins it to those two headers)
         self.by_header = {h: parse_header(h) for h in HEADERS}
         self.protos = {**self.by_header[HEADER], **self.by_header[EVAL_HEADER]}
-        for name, (rt, at) in ((n, p) for protos in self.by_header.values() for n, p in protos.items()):
+        self.by_extension = {h: parse_header(h) for h in EXTENSION_HEADERS}
+        for name, (rt, at) in ((n, p) for protos in (*self.by_header.values(), *self.by_extension.values())
+                               for n, p in protos.items()):
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = rt
             fn.argtypes = [t for t, _ in at]

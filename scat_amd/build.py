@@ -24,7 +24,7 @@ def _sources():
 
 
 def _public_headers_mtime():
-    return max(os.path.getmtime(os.path.join(HERE, "..", "include", h)) for h in ("scat_hip.h", "scat_mesh_eval.h", "scat_eval.h", "scat_render.h", "scat_mano.h", "scat_mano_fit.h", "scat_mano_fit_kp.h"))
+    return max(os.path.getmtime(os.path.join(HERE, "..", "include", h)) for h in ("scat_hip.h", "scat_mesh_eval.h", "scat_eval.h", "scat_render.h", "scat_mano.h", "scat_mano_fit.h", "scat_mano_fit_kp.h", "scat_mano_fit_seq.h"))
 
 
 def _deps_mtime():

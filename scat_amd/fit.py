@@ -13,6 +13,13 @@ Geman-McClure loss and joint limits, and solves for the weak-perspective camera 
     res = fitter.fit_keypoints(joints2d=kp2d, sigma2=10.0)     # KeypointFitResult(..., cam, cost, accepted, p)
     frames = renderer.render(fitter.mesh(res), res.cam)        # lands on the keypoints
 
+fit_sequence (include/scat_mano_fit_seq.h, csrc/mano_fit_seq.hip) fits a track of frames in one solve, consecutive frames
+tied by a smoothness penalty that decides what 21 joints leave free (twist, a shape that flickers) and bridges frames
+without data:
+
+    res = fitter.fit_sequence(joints, smooth=dict(rots=1e-4, poses=1e-4, betas=1e-2, trans=1e-1, scale=1e-1))
+    verts = fitter.mesh(res)                           # [S,T,V,3]
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -28,6 +35,8 @@ UNKNOWNS = 62                  # rots 3, poses 45, betas 10, trans 3, log_scale 
 MAX_ITERS = 64                 # SCAT_FIT_MAX_ITERS
 ALL_FREE = (1 << UNKNOWNS) - 1
 KP_UNKNOWNS = 65               # the 62, then the camera cs, ctx, cty: SCAT_FIT_KP_UNKNOWNS
+SEQ_MAX_T = 256                # SCAT_FIT_SEQ_MAX_T
+SMOOTH_KEYS = ("rots", "poses", "betas", "trans", "scale")      # s_rots .. s_scale, in the entry point's order
 SLICES = {"rots": slice(0, 3), "poses": slice(3, 48), "betas": slice(48, 58), "trans": slice(58, 61), "log_scale": slice(61, 62)}
 
 
@@ -64,6 +73,17 @@ class KeypointFitResult(NamedTuple):
     p: torch.Tensor          # [B,65]: the six groups as the kernel holds them (log_scale, then the camera, last)
 
 
+class SequenceFitResult(NamedTuple):
+    rots: torch.Tensor       # [S,T,3]
+    poses: torch.Tensor      # [S,T,45]
+    betas: torch.Tensor      # [S,T,10]
+    trans: torch.Tensor      # [S,T,3]
+    scale: torch.Tensor      # [S,T]
+    cost: torch.Tensor       # [S], +inf for a sequence with a target or weight that was not finite
+    accepted: torch.Tensor   # [S] int32
+    p: torch.Tensor          # [S,T,62]: the five groups as the kernel holds them (log_scale last)
+
+
 def _check_model(what, model, ref):
     if model.device is None or model.device != ref.device:
         raise ScatError(f"{what}: the model is on {model.device}, the inputs on {ref.device}: call ManoModel.to first")
@@ -85,6 +105,21 @@ def _check_ranges(what, iters, masks_ok, and_cam=""):
         raise ScatError(f"{what}: {iters} iterations outside 1..{MAX_ITERS}")
     if not masks_ok:
         raise ScatError(f"{what}: free has bits above {UNKNOWNS - 1} set{and_cam}")
+
+
+def _smooth(what, smooth):
+    """the five smoothness weights in the entry point's order, from a dict with keys among SMOOTH_KEYS"""
+    import math
+
+    smooth = {} if smooth is None else dict(smooth)
+    unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
+    if unknown:
+        raise ScatError(f"{what}: unknown smooth keys {unknown}, the groups are {list(SMOOTH_KEYS)}")
+    out = tuple(float(smooth.get(k, 0.0)) for k in SMOOTH_KEYS)
+    for k, v in zip(SMOOTH_KEYS, out):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ScatError(f"{what}: smooth[{k!r}] = {v} must be finite and not negative")
+    return out
 
 
 def _groups(p):
@@ -134,6 +169,24 @@ def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_l
                            _p(pose_hi), _p(p), _p(cost), _p(accepted), B, model.V, model.parents_packed, *model.tips, int(iters),
                            int(init), float(lambda0), float(w_pose), float(w_beta), float(w_limit), float(sigma3), float(sigma2),
                            float(half_w), float(half_h), int(free), int(free_cam), _stream())
+    return cost, accepted
+
+
+def mano_fit_seq(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose, w_beta, s_rots, s_poses, s_betas, s_trans,
+                 s_scale, free=ALL_FREE):
+    """scat_mano_fit_seq as it is declared: targets [S,T,21,3], weights [S,T,21] or None, joint_map int32 [21] on the
+    device, p [S,T,62] (read when init = 0, written) -> (cost [S], accepted [S] int32).  The workspace is allocated here,
+    at the size scat_mano_fit_seq_ws gives (0 for sizes the launch refuses)."""
+    S, T = int(targets.shape[0]), int(targets.shape[1])
+    cost = torch.empty((S,), dtype=torch.float32, device=targets.device)
+    accepted = torch.empty((S,), dtype=torch.int32, device=targets.device)
+    L = lib()
+    nbytes = int(L.scat_mano_fit_seq_ws(S, T))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=targets.device)
+    L.scat_mano_fit_seq(*_model_args(model), _p(targets), _p(weights), _p(joint_map), _p(p), _p(cost), _p(accepted), _p(ws), nbytes, S,
+                        T, model.V, model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose),
+                        float(w_beta), float(s_rots), float(s_poses), float(s_betas), float(s_trans), float(s_scale), int(free),
+                        _stream())
     return cost, accepted
 
 
@@ -187,6 +240,55 @@ class ManoFitter:
         if out66.dim() != 2 or out66.shape[1] != 66:
             raise ScatError(f"fit_outputs needs the network's output [B,66], got {tuple(out66.shape)}")
         return self.fit(out66.detach()[:, 3:].reshape(-1, 21, 3).contiguous(), weights)
+
+    def fit_sequence(self, joints, weights=None, smooth=None, init=None, free=ALL_FREE, iters=None):
+        """joints [S,T,21,3] fp32, S sequences of T <= 256 frames -> SequenceFitResult.  The frames of a sequence are fitted
+        in one Levenberg-Marquardt solve, with the penalty sum_i d_i (p_t,i - p_t-1,i)^2 between consecutive frames.
+        smooth: dict(rots=, poses=, betas=, trans=, scale=), the weight d of each group; a key left out is 0, and all
+        zero decouples the frames.  UNITS: the data term is in the joints' unit squared, and each weight multiplies a
+        squared difference in the unknown's own unit: radians squared for rots and poses (the penalty is on the
+        axis-angle numbers, not on the rotations), the shape coefficients' for betas, the joints' unit for trans, a
+        log-ratio for scale.  With joints in metres, rots = 1e-4 counts 0.1 rad per frame like a 1 mm residual.
+        weights: [S,T,21] or None (all ones).  A frame whose weights are all zero is legal whatever its finite joints:
+        it has no data term and is bridged by its neighbours; this is also how a short clip is padded to T frames.
+        init: None for the frame-by-frame Procrustes start (continuous in rots; a zero-weight frame takes its
+        neighbour's), or p [S,T,62] / a SequenceFitResult (it is not modified).  free: bit i clear freezes unknown i in
+        every frame.  A sequence with a joint or weight that is not finite, or a negative weight, in any frame is not
+        fitted: cost +inf, accepted 0, p its start (zeros for the Procrustes start)."""
+        what = "ManoFitter.fit_sequence"
+        sm = _smooth(what, smooth)
+        _need_gpu(what, joints, *(() if weights is None else (weights,)))
+        _check_model(what, self.model, joints)
+        if joints.dim() != 4 or joints.shape[0] == 0 or not 1 <= joints.shape[1] <= SEQ_MAX_T or tuple(joints.shape[2:]) != (21, 3) \
+                or joints.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 joints [S,T,21,3] with S >= 1 and T in 1..{SEQ_MAX_T}, got {joints.dtype} "
+                            f"{tuple(joints.shape)}")
+        S, T = int(joints.shape[0]), int(joints.shape[1])
+        if weights is not None and (tuple(weights.shape) != (S, T, 21) or weights.dtype != torch.float32):
+            raise ScatError(f"{what} needs fp32 weights [{S},{T},21], got {weights.dtype} {tuple(weights.shape)}")
+        if init is None:
+            p = torch.empty((S, T, UNKNOWNS), dtype=torch.float32, device=joints.device)
+        else:
+            p0 = init.p if isinstance(init, SequenceFitResult) else init
+            _need_gpu(what, p0)
+            if tuple(p0.shape) != (S, T, UNKNOWNS) or p0.dtype != torch.float32:
+                raise ScatError(f"{what} needs an fp32 start [{S},{T},{UNKNOWNS}], got {p0.dtype} {tuple(p0.shape)}")
+            p = p0.clone().contiguous()
+        iters = self.iters if iters is None else int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        cost, accepted = mano_fit_seq(self.model, joints.contiguous(), None if weights is None else weights.contiguous(),
+                                      self._map_on(joints.device), p, iters, 0 if init is not None else 1, self.lambda0,
+                                      self.w_pose, self.w_beta, *sm, free)
+        return SequenceFitResult(p[..., 0:3], p[..., 3:48], p[..., 48:58], p[..., 58:61], torch.exp(p[..., 61]), cost, accepted, p)
+
+    def fit_outputs_sequence(self, out66, weights=None, smooth=None):
+        """out66 [S,T,66]: the network's camera and 21 root-relative joints for every frame of S tracks; the joints are
+        fitted as sequences (fit_sequence), the cameras are the caller's to pass on to the renderer"""
+        _need_gpu("ManoFitter.fit_outputs_sequence", out66)
+        if out66.dim() != 3 or out66.shape[2] != 66:
+            raise ScatError(f"fit_outputs_sequence needs the network's outputs [S,T,66], got {tuple(out66.shape)}")
+        S, T = out66.shape[:2]
+        return self.fit_sequence(out66.detach()[:, :, 3:].reshape(S, T, 21, 3).contiguous(), weights, smooth)
 
     def fit_keypoints(self, joints3d=None, joints2d=None, w3=None, w2=None, size=(224, 224), sigma3=0.0, sigma2=0.0, limits=None,
                       w_limit=0.0, init=None, free=None, free_cam=7, iters=None):
@@ -245,16 +347,22 @@ class ManoFitter:
         return project_outputs(torch.cat([result.cam, j.reshape(j.shape[0], 63)], dim=1), int(size[0]), int(size[1]))
 
     def joints(self, result):
-        """the fitted joints [B,21,3] in the targets' frame and order"""
+        """the fitted joints [B,21,3] in the targets' frame and order; [S,T,21,3] for a SequenceFitResult"""
         return self._posed(result)[0]
 
     def mesh(self, result):
-        """the fitted mesh [B,V,3] in the targets' frame: scale x vertices + trans, through scat_mano_fwd"""
+        """the fitted mesh [B,V,3] in the targets' frame: scale x vertices + trans, through scat_mano_fwd; [S,T,V,3] for a
+        SequenceFitResult"""
         return self._posed(result)[1]
 
     def _posed(self, r):
         _need_gpu("ManoFitter.mesh", r.p)
         _check_model("ManoFitter.mesh", self.model, r.p)
+        if isinstance(r, SequenceFitResult):      # every frame as one batch, then back to [S,T,...]
+            S, T = r.p.shape[:2]
+            p = r.p.reshape(S * T, UNKNOWNS)
+            j, v = self._posed(FitResult(*_groups(p), r.cost, r.accepted, p))
+            return j.reshape(S, T, 21, 3), v.reshape(S, T, -1, 3)
         out = mano_fwd(self.model, r.rots.contiguous(), r.poses.contiguous(), r.betas.contiguous())
         out = r.scale[:, None, None] * out + r.trans[:, None, :]
         return out[:, :21][:, self._map_on(out.device).long()], out[:, 21:].contiguous()
