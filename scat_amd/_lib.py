@@ -2,7 +2,8 @@
 (the train step), scat_mesh_eval.h (on-device mesh scoring), scat_eval.h (on-device evaluation), scat_mano_fit_kp.h (the MANO fit to 2-D and 3-D keypoints),
 scat_mano_fit.h (the MANO fit), scat_render.h (the mesh and skeleton renderer) and scat_mano.h (the MANO layer), so the
 headers are the single source of truth for the C ABI. EXTENSION_HEADERS (scat_mano_fit_seq.h, the MANO fit to a track of
-frames) are bound the same way beside them. The product path has NO fallback: if the library is missing, importing a kernel raises."""
+frames) are bound the same way beside them, and _Lib.bind(path) binds any further header of the library on first use
+(scat_mano_fit_verts.h, the MANO fit to a full mesh, from scat_amd/fit.py). The product path has NO fallback: if the library is missing, importing a kernel raises."""
 from __future__ import annotations
 
 import ctypes
@@ -84,16 +85,37 @@ class _Lib:
         self.by_header = {h: parse_header(h) for h in HEADERS}
         self.protos = {**self.by_header[HEADER], **self.by_header[EVAL_HEADER]}
         self.by_extension = {h: parse_header(h) for h in EXTENSION_HEADERS}
-        for name, (rt, at) in ((n, p) for protos in (*self.by_header.values(), *self.by_extension.values())
-                               for n, p in protos.items()):
-            fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
-            fn.restype = rt
-            fn.argtypes = [t for t, _ in at]
-            if rt is ctypes.c_int and name not in ("scat_version", "scat_get_math_mode", "scat_epilogue_stats_groups",
-                                                      "scat_epilogue_bnb_groups"):
-                setattr(self, name, self._checked(fn, name))
-            else:
-                setattr(self, name, fn)
+        self.bound = {}      # bind(): {header path: namespace of its entry points}
+        for name, proto in ((n, p) for protos in (*self.by_header.values(), *self.by_extension.values())
+                            for n, p in protos.items()):
+            setattr(self, name, self._resolve(name, proto))
+
+    def _resolve(self, name, proto):
+        """the library's symbol `name` with the parsed prototype; an int return goes through the checked wrapper"""
+        rt, at = proto
+        fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
+        fn.restype = rt
+        fn.argtypes = [t for t, _ in at]
+        if rt is ctypes.c_int and name not in ("scat_version", "scat_get_math_mode", "scat_epilogue_stats_groups",
+                                                  "scat_epilogue_bnb_groups"):
+            return self._checked(fn, name)
+        return fn
+
+    def bind(self, header_path):
+        """-> a namespace with one callable per entry point that the header declares, bound like those of HEADERS (parsed
+        prototypes, the checked wrapper on int returns); a declared symbol that the library lacks raises AttributeError
+        naming it.  Cached in self.bound by path; HEADERS, EXTENSION_HEADERS and their tables are not touched."""
+        if header_path not in self.bound:
+            import types
+
+            fns = {}
+            for name, proto in parse_header(header_path).items():
+                try:
+                    fns[name] = self._resolve(name, proto)
+                except AttributeError:
+                    raise AttributeError(f"{LIBPATH} lacks {name}, which {header_path} declares") from None
+            self.bound[header_path] = types.SimpleNamespace(**fns)
+        return self.bound[header_path]
 
     def _checked(self, fn, name):
         last = self.cdll.scat_last_error

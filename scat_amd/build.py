@@ -23,8 +23,15 @@ def _sources():
     return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+# The public headers the library ships; build() refuses to build without one of them.  The rebuild trigger below lists
+# include/ instead, so a header added later counts before anyone names it here.
+PUBLIC_HEADERS = ("scat_hip.h", "scat_mesh_eval.h", "scat_eval.h", "scat_render.h", "scat_mano.h", "scat_mano_fit.h",
+                  "scat_mano_fit_kp.h", "scat_mano_fit_seq.h", "scat_mano_fit_verts.h")
+INCLUDE = os.path.join(HERE, "..", "include")
+
+
 def _public_headers_mtime():
-    return max(os.path.getmtime(os.path.join(HERE, "..", "include", h)) for h in ("scat_hip.h", "scat_mesh_eval.h", "scat_eval.h", "scat_render.h", "scat_mano.h", "scat_mano_fit.h", "scat_mano_fit_kp.h", "scat_mano_fit_seq.h"))
+    return max(os.path.getmtime(os.path.join(INCLUDE, h)) for h in os.listdir(INCLUDE) if h.endswith(".h"))
 
 
 def _deps_mtime():
@@ -57,6 +64,9 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
         finally:
             OUT, OBJ = saved[0], saved[1]
             FLAGS[:] = saved[2]
+    missing = [h for h in PUBLIC_HEADERS if not os.path.exists(os.path.join(INCLUDE, h))]
+    if missing:
+        raise RuntimeError(f"public headers missing from {os.path.abspath(INCLUDE)}: {missing}")
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _deps_mtime():
         return OUT
     os.makedirs(OBJ, exist_ok=True)

@@ -20,14 +20,21 @@ without data:
     res = fitter.fit_sequence(joints, smooth=dict(rots=1e-4, poses=1e-4, betas=1e-2, trans=1e-1, scale=1e-1))
     verts = fitter.mesh(res)                           # [S,T,V,3]
 
+fit_vertices (include/scat_mano_fit_verts.h, csrc/mano_fit_verts.hip) takes a mesh in the model's topology, which decides
+the twist and the shape that 21 joints leave open; a joints fit of the same hand is its natural warm start:
+
+    res = fitter.fit_vertices(verts)                   # FitResult; verts [B,V,3], vertex v is the model's vertex v
+    res = fitter.fit_vertices(verts, init=fitter.fit(joints))
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
+import os
 from typing import NamedTuple
 
 import torch
 
-from ._lib import ScatError, lib
+from ._lib import HERE, ScatError, lib
 from .mano import BETAS, POSE, ManoModel, _model_args, _need_gpu, mano_fwd
 from .ops import _p, _stream
 
@@ -37,6 +44,8 @@ ALL_FREE = (1 << UNKNOWNS) - 1
 KP_UNKNOWNS = 65               # the 62, then the camera cs, ctx, cty: SCAT_FIT_KP_UNKNOWNS
 SEQ_MAX_T = 256                # SCAT_FIT_SEQ_MAX_T
 SMOOTH_KEYS = ("rots", "poses", "betas", "trans", "scale")      # s_rots .. s_scale, in the entry point's order
+# bound on first use by lib().bind, beside _lib.py's tables: the MANO fit to a full mesh
+FIT_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_verts.h")
 SLICES = {"rots": slice(0, 3), "poses": slice(3, 48), "betas": slice(48, 58), "trans": slice(58, 61), "log_scale": slice(61, 62)}
 
 
@@ -157,6 +166,37 @@ def mano_fit(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose
     return cost, accepted
 
 
+def mano_verts_jac(model, rots, poses, betas):
+    """-> (verts [B,V,3], jac [B,3V,58]): the mesh of mano_fwd (its rows 21..) and d verts / d (rots, poses, betas), one
+    launch"""
+    _need_gpu("mano_verts_jac", rots, poses, betas)
+    _check_model("mano_verts_jac", model, rots)
+    B = rots.shape[0]
+    if B == 0 or tuple(rots.shape) != (B, 3) or tuple(poses.shape) != (B, POSE) or tuple(betas.shape) != (B, BETAS):
+        raise ScatError(f"mano_verts_jac needs rots [B,3], poses [B,45], betas [B,10] with B >= 1, got {tuple(rots.shape)}, "
+                        f"{tuple(poses.shape)}, {tuple(betas.shape)}")
+    if not all(t.dtype == torch.float32 for t in (rots, poses, betas)):
+        raise ScatError("mano_verts_jac needs fp32 tensors")
+    rots, poses, betas = rots.contiguous(), poses.contiguous(), betas.contiguous()
+    verts = torch.empty((B, model.V, 3), dtype=torch.float32, device=rots.device)
+    jac = torch.empty((B, 3 * model.V, 58), dtype=torch.float32, device=rots.device)
+    lib().bind(FIT_VERTS_HEADER).scat_mano_verts_jac(*_model_args(model), _p(rots), _p(poses), _p(betas), _p(verts), _p(jac), B,
+                                                     model.V, model.parents_packed, _stream())
+    return verts, jac
+
+
+def mano_fit_verts(model, targets, weights, p, iters, init, lambda0, w_pose, w_beta, free=ALL_FREE):
+    """scat_mano_fit_verts as it is declared: targets [B,V,3], weights [B,V] or None, p [B,62] (read when init = 0,
+    written) -> (cost [B], accepted [B] int32)"""
+    B = targets.shape[0]
+    cost = torch.empty((B,), dtype=torch.float32, device=targets.device)
+    accepted = torch.empty((B,), dtype=torch.int32, device=targets.device)
+    lib().bind(FIT_VERTS_HEADER).scat_mano_fit_verts(*_model_args(model), _p(targets), _p(weights), _p(p), _p(cost), _p(accepted), B,
+                                                     model.V, model.parents_packed, int(iters), int(init), float(lambda0),
+                                                     float(w_pose), float(w_beta), int(free), _stream())
+    return cost, accepted
+
+
 def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
                 w_beta, w_limit, sigma3, sigma2, half_w, half_h, free=ALL_FREE, free_cam=7):
     """scat_mano_fit_kp as it is declared: targets3 [B,21,3] / weights3 [B,21], targets2 [B,21,2] / weights2 [B,21] (None
@@ -240,6 +280,35 @@ class ManoFitter:
         if out66.dim() != 2 or out66.shape[1] != 66:
             raise ScatError(f"fit_outputs needs the network's output [B,66], got {tuple(out66.shape)}")
         return self.fit(out66.detach()[:, 3:].reshape(-1, 21, 3).contiguous(), weights)
+
+    def fit_vertices(self, verts, weights=None, init=None, free=ALL_FREE, iters=None):
+        """verts [B,V,3] fp32, a mesh in the model's topology (vertex v is the model's vertex v; joint_map plays no part)
+        -> FitResult.  weights: [B,V] or None (all ones); a vertex of weight 0 does not count.  init: None for the
+        Procrustes start over the vertices, or p [B,62] / any FitResult to start from (it is not modified): a joints fit
+        of the same hand is the natural warm start.  free: bit i clear freezes unknown i (free_mask()).  A hand whose
+        vertices or weights are not finite, or that has a negative weight, is not fitted: its cost is +inf, its accepted
+        count 0 and its p the start (zeros for the Procrustes start)."""
+        what = "ManoFitter.fit_vertices"
+        _need_gpu(what, verts, *(() if weights is None else (weights,)))
+        _check_model(what, self.model, verts)
+        B, V = verts.shape[0], self.model.V
+        if B == 0 or tuple(verts.shape) != (B, V, 3) or verts.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 verts [B,{V},3] with B >= 1, got {verts.dtype} {tuple(verts.shape)}")
+        if weights is not None and (tuple(weights.shape) != (B, V) or weights.dtype != torch.float32):
+            raise ScatError(f"{what} needs fp32 weights [{B},{V}], got {weights.dtype} {tuple(weights.shape)}")
+        p = _start(what, init, FitResult, B, UNKNOWNS, verts.device)
+        iters = self.iters if iters is None else int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        cost, accepted = mano_fit_verts(self.model, verts.contiguous(), None if weights is None else weights.contiguous(), p,
+                                        iters, 0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, free)
+        return FitResult(*_groups(p), cost, accepted, p)
+
+    def fit_mesh_outputs(self, out, weights=None):
+        """out [B,21+V,3]: joints and mesh in the layout of ManoLayer / scat_mano_fwd; the V vertex rows are fitted"""
+        _need_gpu("ManoFitter.fit_mesh_outputs", out)
+        if out.dim() != 3 or tuple(out.shape[1:]) != (21 + self.model.V, 3):
+            raise ScatError(f"fit_mesh_outputs needs the layer's output [B,{21 + self.model.V},3], got {tuple(out.shape)}")
+        return self.fit_vertices(out.detach()[:, 21:].contiguous(), weights)
 
     def fit_sequence(self, joints, weights=None, smooth=None, init=None, free=ALL_FREE, iters=None):
         """joints [S,T,21,3] fp32, S sequences of T <= 256 frames -> SequenceFitResult.  The frames of a sequence are fitted
