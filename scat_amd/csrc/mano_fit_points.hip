@@ -1,0 +1,405 @@
+// The MANO fit to an unordered point cloud, include/scat_mano_fit_points.h: the correspondence kernel between the layer
+// and scat_mano_fit_verts, and the loop of launches around the two.  One workgroup of 256 threads per hand.
+//
+// cloud_assign_kernel<kParams>, one template in two forms:
+//   model points   kParams: p[b] into LDS, a ManoArgs pointed at it (b = 0) as vfit_cost does, mano_setup, then
+//                  mano_vertex, x = Rg d and exp(p[61]) x + trans for every vertex, into LDS as x / y / z arrays and
+//                  into model_pts.  Otherwise the caller's verts are copied there.
+//   nearest vertex a thread takes the points tid, tid + 256, ..., four at a time, and walks all V vertices once for the
+//                  four: every lane reads the same LDS address, a broadcast (mesh_eval.hip's nn_walk, with the index
+//                  kept beside the minimum).  fp64 on the fp32 numbers, contraction off, strict < ascending.  The vertex
+//                  of a matched point goes into an LDS index array of N ints, -1 for the others.
+//   reduction      a thread takes the vertices tid, tid + 256, ... and scans the index array once per vertex, n
+//                  ascending (four indices per LDS read), adding w, w q and w d2 of its points in fp64 (d2 recomputed by the walk's expression: the
+//                  same bits).  The three totals of stats: each thread's vertices ascending, an xor butterfly over the
+//                  wavefront, the four wavefronts ascending.
+// Static LDS at the largest sizes: 18 KiB of vertices, 32 KiB of indices, 2.6 KiB of pose state: 53 KiB of the 64.
+// scat_mano_fit_points launches {assign, scat_mano_fit_verts} `rounds` times and one last assign; each assign after the
+// first adds the accepted count of the fit before it to the caller's total.
+#include "mano_fit_common.h"
+
+#include "../../include/scat_mano_fit_points.h"
+
+namespace scat {
+
+constexpr int kPMaxN = SCAT_FIT_POINTS_MAX_N;
+constexpr int kPQ = 4;                      // points a thread walks at once
+constexpr int kPWaves = kFThreads / 64;
+static_assert(kPWaves == 4, "the totals add four wavefronts");
+
+struct CloudArgs {
+    ManoArgs m;            // kParams; rots / poses / betas are set by the kernel (LDS)
+    const float* p;        // kParams: [B,62]
+    const float* verts;    // otherwise: [B,V,3]
+    const float* points;   // [B,N,3]
+    const float* weights;  // [B,N] or null
+    float max_dist;
+    float* model_pts;      // kParams: [B,V,3] or null
+    int* idx;              // [B,N]
+    float* dist;           // [B,N]
+    float* vw;             // [B,V]
+    float* vtarget;        // [B,V,3]
+    double* stats;         // [B,4]
+    // scat_mano_fit_points: fold 1 zeroes acc_total, fold 2 adds the round's count to it; data_cost from the last assign
+    const int* acc_round;
+    int* acc_total;
+    float* data_cost;
+    int fold;
+    int N, V;
+};
+
+template <bool kParams>
+struct CloudPose {};
+template <>
+struct CloudPose<true> {
+    ManoPose s;
+    float p[kFU];
+};
+
+// the squared distance of the walk and of the data cost: every product and sum rounded once
+__device__ __forceinline__ double cloud_d2(double qx, double qy, double qz, double x, double y, double z) {
+#pragma clang fp contract(off)
+    const double dx = qx - x, dy = qy - y, dz = qz - z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// each of NQ points against all V vertices, ascending; the vertex address is wave-uniform
+template <int NQ>
+__device__ __forceinline__ void cloud_walk(const double (&qx)[kPQ], const double (&qy)[kPQ], const double (&qz)[kPQ],
+                                           const float (*mp)[kMMaxV], int V, double (&best)[kPQ], int (&bi)[kPQ]) {
+#pragma unroll 4
+    for (int j = 0; j < V; ++j) {
+        const double x = (double)mp[0][j], y = (double)mp[1][j], z = (double)mp[2][j];
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) {
+            const double d2 = cloud_d2(qx[k], qy[k], qz[k], x, y, z);
+            if (d2 < best[k]) {
+                best[k] = d2;
+                bi[k] = j;
+            }
+        }
+    }
+}
+
+// a hand that is not assigned.  All threads
+__device__ __forceinline__ void cloud_unusable(const CloudArgs& a, int64_t b, bool zero_model) {
+    const int tid = threadIdx.x, N = a.N, V = a.V;
+    for (int n = tid; n < N; n += kFThreads) {
+        a.idx[b * N + n] = -1;
+        a.dist[b * N + n] = 0.f;
+    }
+    for (int v = tid; v < V; v += kFThreads) a.vw[b * V + v] = NAN;
+    for (int i = tid; i < 3 * V; i += kFThreads) {
+        a.vtarget[b * 3 * V + i] = 0.f;
+        if (zero_model && a.model_pts) a.model_pts[b * 3 * V + i] = 0.f;
+    }
+    if (tid == 0) {
+        double* st = a.stats + b * 4;
+        st[0] = 2.0, st[1] = 0.0, st[2] = 0.0, st[3] = __builtin_huge_val();
+        if (a.data_cost) a.data_cost[b] = INFINITY;
+    }
+}
+
+// grid = B, block = 256
+template <bool kParams>
+__global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
+    __shared__ float mp[3][kMMaxV];      // the model points, x / y / z
+    __shared__ alignas(16) int sidx[kPMaxN];   // the vertex of a matched point, -1 otherwise; read four at a time
+    __shared__ CloudPose<kParams> ps;
+    __shared__ double red[3][kPWaves];
+    static_assert(sizeof(mp) + sizeof(sidx) + sizeof(CloudPose<kParams>) + sizeof(red) <= 64 * 1024, "static LDS");
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x, N = a.N, V = a.V;
+    const float* pts = a.points + b * 3 * (int64_t)N;
+    const float* wts = a.weights ? a.weights + b * (int64_t)N : nullptr;
+    if (tid == 0 && a.fold) a.acc_total[b] = a.fold == 1 ? 0 : a.acc_total[b] + a.acc_round[b];
+
+    int bad = 0;
+    for (int i = tid; i < 3 * N; i += kFThreads) bad |= !fit_finite(pts[i]);
+    if (wts) {
+        for (int i = tid; i < N; i += kFThreads) bad |= !(fit_finite(wts[i]) && wts[i] >= 0.f);
+    }
+    if constexpr (kParams) {
+        if (tid < kFU) {
+            const float v = a.p[b * kFU + tid];
+            ps.p[tid] = v;
+            bad |= !fit_finite(v);
+        }
+    }
+    if (__syncthreads_or(bad)) {   // the same for every thread of the workgroup
+        cloud_unusable(a, b, true);
+        return;
+    }
+
+    // the model points
+    bad = 0;
+    if constexpr (kParams) {
+        ManoArgs pm = a.m;
+        pm.rots = ps.p, pm.poses = ps.p + 3, pm.betas = ps.p + 3 + kFPose;
+        mano_setup(ps.s, pm, 0);
+        const float sc = expf(ps.p[kFU - 1]);
+        float Rg[9], tr[3];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rg[e] = ps.s.Rg[e];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tr[c] = ps.p[kFModel + c];
+        for (int v = tid; v < V; v += kFThreads) {
+            float vp[3], T[9], d[3], x[3];
+            mano_vertex(ps.s, pm, v, vp, T, d);
+            mv(Rg, d, x);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float mc = sc * x[c] + tr[c];
+                mp[c][v] = mc;
+                bad |= !fit_finite(mc);
+                if (a.model_pts) a.model_pts[(b * V + v) * 3 + c] = mc;
+            }
+        }
+    } else {
+        const float* vs = a.verts + b * 3 * (int64_t)V;
+        for (int i = tid; i < 3 * V; i += kFThreads) {
+            const int v = i / 3, c = i - 3 * v;
+            const float mc = vs[i];
+            mp[c][v] = mc;
+            bad |= !fit_finite(mc);
+        }
+    }
+    if (__syncthreads_or(bad)) {   // (also the barrier that publishes mp)
+        cloud_unusable(a, b, false);
+        return;
+    }
+
+    // the nearest vertex of every point
+    const double md2 = (double)a.max_dist * (double)a.max_dist;
+    for (int n0 = 0; n0 < N; n0 += kPQ * kFThreads) {
+        const int nq = min(kPQ, (N - n0 + kFThreads - 1) / kFThreads);   // slots with a point in them: workgroup-uniform
+        bool live[kPQ];
+        double qx[kPQ], qy[kPQ], qz[kPQ], best[kPQ];
+        int bi[kPQ];
+#pragma unroll
+        for (int k = 0; k < kPQ; ++k) {
+            const int n = n0 + k * kFThreads + tid;
+            live[k] = n < N && (wts ? wts[n] : 1.f) > 0.f;
+            qx[k] = live[k] ? (double)pts[3 * n] : 0.0;
+            qy[k] = live[k] ? (double)pts[3 * n + 1] : 0.0;
+            qz[k] = live[k] ? (double)pts[3 * n + 2] : 0.0;
+            best[k] = __builtin_huge_val();
+            bi[k] = 0;
+        }
+        switch (nq) {
+            case 1: cloud_walk<1>(qx, qy, qz, mp, V, best, bi); break;
+            case 2: cloud_walk<2>(qx, qy, qz, mp, V, best, bi); break;
+            case 3: cloud_walk<3>(qx, qy, qz, mp, V, best, bi); break;
+            default: cloud_walk<4>(qx, qy, qz, mp, V, best, bi); break;
+        }
+#pragma unroll
+        for (int k = 0; k < kPQ; ++k) {
+            const int n = n0 + k * kFThreads + tid;
+            if (n >= N) continue;
+            a.idx[b * N + n] = live[k] ? bi[k] : -1;
+            a.dist[b * N + n] = live[k] ? (float)sqrt(best[k]) : 0.f;
+            sidx[n] = (live[k] && best[k] <= md2) ? bi[k] : -1;
+        }
+    }
+    if (tid < 3 && N + tid < ((N + 3) & ~3)) sidx[N + tid] = -1;   // the last group of four
+    __syncthreads();
+
+    // per vertex: weight, centroid and cost of its matched points, n ascending
+    double tot[3] = {0.0, 0.0, 0.0};   // matched weight, matched count, data cost
+    for (int v = tid; v < V; v += kFThreads) {
+        const double x = (double)mp[0][v], y = (double)mp[1][v], z = (double)mp[2][v];
+        double W = 0.0, S[3] = {0.0, 0.0, 0.0}, C = 0.0;
+        int cnt = 0;
+        const auto take = [&](int n) {
+            const double w = wts ? (double)wts[n] : 1.0;
+            const double q0 = (double)pts[3 * n], q1 = (double)pts[3 * n + 1], q2 = (double)pts[3 * n + 2];
+            W += w;
+            S[0] += w * q0, S[1] += w * q1, S[2] += w * q2;   // fp32 x fp32: the products are exact in fp64
+            C += w * cloud_d2(q0, q1, q2, x, y, z);
+            ++cnt;
+        };
+        // four indices per LDS read, two reads in flight: one index per read made a scan 130 cycles per point, the
+        // latency of the read, and the scans two thirds of the kernel (profiles/fit_points_bench.txt)
+        const int4* s4 = reinterpret_cast<const int4*>(sidx);
+        const int groups = (N + 3) >> 2;
+#pragma unroll 2
+        for (int g = 0; g < groups; ++g) {
+            const int4 c = s4[g];
+            if (c.x == v || c.y == v || c.z == v || c.w == v) {
+                if (c.x == v) take(4 * g);
+                if (c.y == v) take(4 * g + 1);
+                if (c.z == v) take(4 * g + 2);
+                if (c.w == v) take(4 * g + 3);
+            }
+        }
+        a.vw[b * V + v] = (float)W;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.vtarget[(b * V + v) * 3 + c] = W > 0.0 ? (float)(S[c] / W) : 0.f;
+        tot[0] += W, tot[1] += (double)cnt, tot[2] += C;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double t = tot[i];
+        for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+        if ((tid & 63) == 0) red[i][tid >> 6] = t;
+    }
+    __syncthreads();
+    const double mw = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];   // the same bits on every thread
+    if (!(mw > 0.0)) {   // nothing matched: the fit is to leave this hand alone
+        for (int v = tid; v < V; v += kFThreads) a.vw[b * V + v] = NAN;   // each thread over the entries it wrote itself
+    }
+    if (tid == 0) {
+        const double dc = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
+        double* st = a.stats + b * 4;
+        st[0] = 0.0;
+        st[1] = mw;
+        st[2] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        st[3] = dc;
+        if (a.data_cost) a.data_cost[b] = (float)dc;
+    }
+}
+
+}  // namespace scat
+
+using namespace scat;
+
+static const int kNoTips[kMTips] = {0, 0, 0, 0, 0};
+
+// what the three entry points check alike, after the pointers that must not be null
+static int cloud_check(const char* fn, const void* const* nullable, int nn, const double* stats, int N, float max_dist) {
+    uintptr_t all = 0;
+    for (int i = 0; i < nn; ++i) all |= (uintptr_t)nullable[i];
+    SCAT_REQUIRE((all & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
+    SCAT_REQUIRE(((uintptr_t)stats & 7) == 0, SCAT_E_ARG, "%s: stats must be 8-byte aligned", fn);
+    SCAT_REQUIRE(N >= 1 && N <= kPMaxN, SCAT_E_SHAPE, "%s: %d points outside 1..%d", fn, N, kPMaxN);
+    SCAT_REQUIRE(max_dist > 0.f, SCAT_E_ARG, "%s: max_dist %g must be positive (+inf: no trim)", fn, (double)max_dist);
+    return SCAT_OK;
+}
+
+template <bool kParams>
+static int cloud_launch(const char* fn, const CloudArgs& a, int B, void* stream) {
+    hipLaunchKernelGGL(cloud_assign_kernel<kParams>, dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
+    SCAT_LAUNCH_CHECK(fn);
+    return SCAT_OK;
+}
+
+extern "C" int scat_cloud_assign(const float* verts, const float* points, const float* weights, float max_dist, int* idx,
+                                 float* dist, float* vw, float* vtarget, double* stats, int B, int N, int V, void* stream) {
+    const char* fn = "scat_cloud_assign";
+    const void* ptrs[] = {verts, points, idx, dist, vw, vtarget, stats};
+    uintptr_t all = 0;
+    for (const void* q : ptrs) {
+        SCAT_REQUIRE(q, SCAT_E_ARG, "%s: null pointer", fn);
+        all |= (uintptr_t)q;
+    }
+    SCAT_REQUIRE((all & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
+    SCAT_REQUIRE(B > 0, SCAT_E_SHAPE, "%s: batch %d must be positive", fn, B);
+    SCAT_REQUIRE(V >= 1 && V <= kMMaxV, SCAT_E_SHAPE, "%s: %d vertices outside 1..%d", fn, V, kMMaxV);
+    const void* nullable[] = {weights};
+    int rc = cloud_check(fn, nullable, 1, stats, N, max_dist);
+    if (rc != SCAT_OK) return rc;
+    CloudArgs a = {};
+    a.verts = verts, a.points = points, a.weights = weights, a.max_dist = max_dist;
+    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
+    rc = cloud_launch<false>(fn, a, B, stream);
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label("cloud_assign_v%d_n%d", V, N);
+    return SCAT_OK;
+}
+
+extern "C" int scat_mano_cloud_assign(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                      const float* hands_mean, const float* p, const float* points, const float* weights,
+                                      float max_dist, float* model_pts, int* idx, float* dist, float* vw, float* vtarget,
+                                      double* stats, int B, int N, int V, uint64_t parents, void* stream) {
+    const char* fn = "scat_mano_cloud_assign";
+    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, p, points, idx, dist, vw, vtarget, stats};
+    CloudArgs a = {};
+    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
+    int rc = mano_validate(fn, ptrs, 12, B, V, parents, kNoTips, &a.m.levels);
+    if (rc != SCAT_OK) return rc;
+    const void* nullable[] = {weights, model_pts};
+    rc = cloud_check(fn, nullable, 2, stats, N, max_dist);
+    if (rc != SCAT_OK) return rc;
+    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist, a.model_pts = model_pts;
+    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
+    rc = cloud_launch<true>(fn, a, B, stream);
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label("mano_cloud_assign_v%d_n%d", V, N);
+    return SCAT_OK;
+}
+
+// the workspace of scat_mano_fit_points: byte offsets, every part rounded up to 16 bytes
+struct PointsWs { int64_t stats, vtarget, vw, cost, acc, idx, dist, total; };
+
+static PointsWs points_ws(int64_t B, int64_t N, int64_t V) {
+    PointsWs w;
+    int64_t off = 0;
+    const auto take = [&off](int64_t bytes) {
+        const int64_t o = off;
+        off += (bytes + 15) & ~(int64_t)15;
+        return o;
+    };
+    w.stats = take(B * 4 * (int64_t)sizeof(double));
+    w.vtarget = take(B * V * 3 * (int64_t)sizeof(float));
+    w.vw = take(B * V * (int64_t)sizeof(float));
+    w.cost = take(B * (int64_t)sizeof(float));
+    w.acc = take(B * (int64_t)sizeof(int));
+    w.idx = take(B * N * (int64_t)sizeof(int));
+    w.dist = take(B * N * (int64_t)sizeof(float));
+    w.total = off;
+    return w;
+}
+
+extern "C" int64_t scat_mano_fit_points_ws(int B, int N, int V) {
+    if (B < 1 || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV) return 0;
+    return points_ws(B, N, V).total;
+}
+
+extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                    const float* hands_mean, const float* points, const float* weights, float* p,
+                                    float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
+                                    int N, int V, uint64_t parents, int rounds, int iters, float max_dist, float lambda0,
+                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
+    const char* fn = "scat_mano_fit_points";
+    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, points, p, data_cost, accepted};
+    CloudArgs a = {};
+    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
+    int rc = mano_validate(fn, ptrs, 9, B, V, parents, kNoTips, &a.m.levels);
+    if (rc != SCAT_OK) return rc;
+    const void* nullable[] = {weights, idx, dist};
+    rc = cloud_check(fn, nullable, 3, nullptr, N, max_dist);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(rounds >= 1 && rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, rounds,
+                 SCAT_FIT_POINTS_MAX_ROUNDS);
+    rc = fit_check_args(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(rounds * iters <= SCAT_FIT_POINTS_MAX_STEPS, SCAT_E_ARG, "%s: %d rounds of %d iterations are more than %d steps",
+                 fn, rounds, iters, SCAT_FIT_POINTS_MAX_STEPS);
+    SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
+    const PointsWs w = points_ws(B, N, V);
+    SCAT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "%s: the workspace must be a 16-byte-aligned pointer", fn);
+    SCAT_REQUIRE(ws_bytes >= w.total, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
+                 (long long)w.total);
+    char* base = static_cast<char*>(ws);
+    float* vtarget = reinterpret_cast<float*>(base + w.vtarget);
+    float* vw = reinterpret_cast<float*>(base + w.vw);
+    float* cost_r = reinterpret_cast<float*>(base + w.cost);
+    int* acc_r = reinterpret_cast<int*>(base + w.acc);
+    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist;
+    a.idx = idx ? idx : reinterpret_cast<int*>(base + w.idx);
+    a.dist = dist ? dist : reinterpret_cast<float*>(base + w.dist);
+    a.vw = vw, a.vtarget = vtarget, a.stats = reinterpret_cast<double*>(base + w.stats);
+    a.acc_round = acc_r, a.acc_total = accepted, a.N = N, a.V = V;
+    for (int r = 0; r <= rounds; ++r) {
+        a.fold = r == 0 ? 1 : 2;
+        a.data_cost = r == rounds ? data_cost : nullptr;
+        rc = cloud_launch<true>(fn, a, B, stream);
+        if (rc != SCAT_OK) return rc;
+        if (r == rounds) break;
+        rc = scat_mano_fit_verts(blend, joint_t, joint_s, weights_t, hands_mean, vtarget, vw, p, cost_r, acc_r, B, V, parents,
+                                 iters, 0, lambda0, w_pose, w_beta, free_mask, stream);
+        if (rc != SCAT_OK) return rc;
+    }
+    set_kernel_label("mano_fit_points_v%d_n%d_r%d_i%d", V, N, rounds, iters);
+    return SCAT_OK;
+}

@@ -26,6 +26,12 @@ the twist and the shape that 21 joints leave open; a joints fit of the same hand
     res = fitter.fit_vertices(verts)                   # FitResult; verts [B,V,3], vertex v is the model's vertex v
     res = fitter.fit_vertices(verts, init=fitter.fit(joints))
 
+fit_points (include/scat_mano_fit_points.h, csrc/mano_fit_points.hip) takes an unordered cloud, a depth camera's or a
+scanner's: nearest-vertex ICP from the caller's start, every round one assignment launch and one fit_vertices launch:
+
+    res = fitter.fit_points(cloud, init=fitter.fit(joints), max_dist=0.03)     # PointFitResult; cloud [B,N,3]
+    corr = fitter.nearest_vertices(res, cloud)         # Correspondences(idx, dist, vertex_weight, vertex_target, ...)
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -35,7 +41,7 @@ from typing import NamedTuple
 import torch
 
 from ._lib import HERE, ScatError, lib
-from .mano import BETAS, POSE, ManoModel, _model_args, _need_gpu, mano_fwd
+from .mano import BETAS, MAX_V, POSE, ManoModel, _model_args, _need_gpu, mano_fwd
 from .ops import _p, _stream
 
 UNKNOWNS = 62                  # rots 3, poses 45, betas 10, trans 3, log_scale 1: SCAT_FIT_UNKNOWNS
@@ -46,6 +52,11 @@ SEQ_MAX_T = 256                # SCAT_FIT_SEQ_MAX_T
 SMOOTH_KEYS = ("rots", "poses", "betas", "trans", "scale")      # s_rots .. s_scale, in the entry point's order
 # bound on first use by lib().bind, beside _lib.py's tables: the MANO fit to a full mesh
 FIT_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_verts.h")
+# likewise: the MANO fit to a point cloud
+FIT_POINTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_points.h")
+POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
+POINTS_MAX_ROUNDS = 64         # SCAT_FIT_POINTS_MAX_ROUNDS
+POINTS_MAX_STEPS = 256         # SCAT_FIT_POINTS_MAX_STEPS: rounds * iters
 SLICES = {"rots": slice(0, 3), "poses": slice(3, 48), "betas": slice(48, 58), "trans": slice(58, 61), "log_scale": slice(61, 62)}
 
 
@@ -93,6 +104,31 @@ class SequenceFitResult(NamedTuple):
     p: torch.Tensor          # [S,T,62]: the five groups as the kernel holds them (log_scale last)
 
 
+class Correspondences(NamedTuple):
+    idx: torch.Tensor             # [B,N] int32: the nearest vertex, -1 for a point of weight 0
+    dist: torch.Tensor            # [B,N]: the distance to it, 0 for a point of weight 0
+    vertex_weight: torch.Tensor   # [B,V]: the matched weight per vertex; a NaN row: unusable, or nothing matched
+    vertex_target: torch.Tensor   # [B,V,3]: the weighted centroid of a vertex's matched points, 0 where it has none
+    matched: torch.Tensor         # [B] int64: matched points
+    matched_weight: torch.Tensor  # [B] fp64
+    data_cost: torch.Tensor       # [B] fp64: sum w d^2 over the matched points, no priors; +inf for an unusable hand
+
+
+class PointFitResult(NamedTuple):
+    rots: torch.Tensor       # [B,3]
+    poses: torch.Tensor      # [B,45]
+    betas: torch.Tensor      # [B,10]
+    trans: torch.Tensor      # [B,3]
+    scale: torch.Tensor      # [B]
+    data_cost: torch.Tensor  # [B]: sum w d^2 over the matched points at p, no priors; +inf for an unusable hand
+    accepted: torch.Tensor   # [B] int32: accepted steps, summed over the rounds
+    p: torch.Tensor          # [B,62]: the five groups as the kernel holds them (log_scale last)
+    matched: torch.Tensor    # [B] int64: matched points at p
+    rms: torch.Tensor        # [B]: sqrt(data_cost / matched weight), +inf when nothing matched
+    idx: torch.Tensor        # [B,N] int32: the nearest vertex at p, -1 for a point of weight 0
+    dist: torch.Tensor       # [B,N]
+
+
 def _check_model(what, model, ref):
     if model.device is None or model.device != ref.device:
         raise ScatError(f"{what}: the model is on {model.device}, the inputs on {ref.device}: call ManoModel.to first")
@@ -102,7 +138,7 @@ def _start(what, init, result_type, B, unknowns, device):
     """the p [B,unknowns] a kernel reads and writes: empty for init None, else a checked copy of init (tensor or result)"""
     if init is None:
         return torch.empty((B, unknowns), dtype=torch.float32, device=device)
-    p0 = init.p if isinstance(init, result_type) else init
+    p0 = init.p if isinstance(init, (result_type, PointFitResult)) else init
     _need_gpu(what, p0)
     if tuple(p0.shape) != (B, unknowns) or p0.dtype != torch.float32:
         raise ScatError(f"{what} needs an fp32 start [{B},{unknowns}], got {p0.dtype} {tuple(p0.shape)}")
@@ -195,6 +231,67 @@ def mano_fit_verts(model, targets, weights, p, iters, init, lambda0, w_pose, w_b
                                                      model.V, model.parents_packed, int(iters), int(init), float(lambda0),
                                                      float(w_pose), float(w_beta), int(free), _stream())
     return cost, accepted
+
+
+def _max_dist(what, max_dist):
+    import math
+
+    d = math.inf if max_dist is None else float(max_dist)
+    if not d > 0.0:
+        raise ScatError(f"{what}: max_dist {max_dist} must be positive (None: no trim)")
+    return d
+
+
+def _cloud_outputs(B, N, V, device):
+    return (torch.empty((B, N), dtype=torch.int32, device=device), torch.empty((B, N), dtype=torch.float32, device=device),
+            torch.empty((B, V), dtype=torch.float32, device=device), torch.empty((B, V, 3), dtype=torch.float32, device=device),
+            torch.empty((B, 4), dtype=torch.float64, device=device))
+
+
+def _correspondences(idx, dist, vw, vtarget, stats):
+    return Correspondences(idx, dist, vw, vtarget, stats[:, 2].long(), stats[:, 1], stats[:, 3])
+
+
+def cloud_assign(verts, points, weights, max_dist):
+    """scat_cloud_assign as it is declared: verts [B,V,3], points [B,N,3], weights [B,N] or None, max_dist > 0 (inf: no
+    trim) -> Correspondences"""
+    B, V, N = verts.shape[0], verts.shape[1], points.shape[1]
+    idx, dist, vw, vtarget, stats = _cloud_outputs(B, N, V, points.device)
+    lib().bind(FIT_POINTS_HEADER).scat_cloud_assign(_p(verts), _p(points), _p(weights), float(max_dist), _p(idx), _p(dist), _p(vw),
+                                                    _p(vtarget), _p(stats), B, N, V, _stream())
+    return _correspondences(idx, dist, vw, vtarget, stats)
+
+
+def mano_cloud_assign(model, p, points, weights, max_dist, want_model_pts=False):
+    """scat_mano_cloud_assign as it is declared: p [B,62], points [B,N,3], weights [B,N] or None -> Correspondences, and
+    with want_model_pts (Correspondences, model_pts [B,V,3])"""
+    B, V, N = p.shape[0], model.V, points.shape[1]
+    idx, dist, vw, vtarget, stats = _cloud_outputs(B, N, V, points.device)
+    mp = torch.empty((B, V, 3), dtype=torch.float32, device=points.device) if want_model_pts else None
+    lib().bind(FIT_POINTS_HEADER).scat_mano_cloud_assign(*_model_args(model), _p(p), _p(points), _p(weights), float(max_dist), _p(mp),
+                                                         _p(idx), _p(dist), _p(vw), _p(vtarget), _p(stats), B, N, V,
+                                                         model.parents_packed, _stream())
+    c = _correspondences(idx, dist, vw, vtarget, stats)
+    return (c, mp) if want_model_pts else c
+
+
+def mano_fit_points(model, points, weights, p, rounds, iters, max_dist, lambda0, w_pose, w_beta, free=ALL_FREE):
+    """scat_mano_fit_points as it is declared: points [B,N,3], weights [B,N] or None, p [B,62] read and written ->
+    (data_cost [B], accepted [B] int32, idx [B,N] int32, dist [B,N], stats [B,4] fp64 of the last assignment).  The
+    workspace is allocated here, at the size scat_mano_fit_points_ws gives (0 for sizes the launch refuses)."""
+    B, N = int(points.shape[0]), int(points.shape[1])
+    dev = points.device
+    cost = torch.empty((B,), dtype=torch.float32, device=dev)
+    accepted = torch.empty((B,), dtype=torch.int32, device=dev)
+    idx = torch.empty((B, N), dtype=torch.int32, device=dev)
+    dist = torch.empty((B, N), dtype=torch.float32, device=dev)
+    ns = lib().bind(FIT_POINTS_HEADER)
+    nbytes = int(ns.scat_mano_fit_points_ws(B, N, model.V))
+    ws = torch.empty((max(nbytes, 32 * B, 16),), dtype=torch.uint8, device=dev)
+    ns.scat_mano_fit_points(*_model_args(model), _p(points), _p(weights), _p(p), _p(cost), _p(accepted), _p(idx), _p(dist), _p(ws),
+                            nbytes, B, N, model.V, model.parents_packed, int(rounds), int(iters), float(max_dist), float(lambda0),
+                            float(w_pose), float(w_beta), int(free), _stream())
+    return cost, accepted, idx, dist, ws[:32 * B].view(torch.float64).reshape(B, 4).clone()
 
 
 def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
@@ -302,6 +399,71 @@ class ManoFitter:
         cost, accepted = mano_fit_verts(self.model, verts.contiguous(), None if weights is None else weights.contiguous(), p,
                                         iters, 0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, free)
         return FitResult(*_groups(p), cost, accepted, p)
+
+    def _cloud(self, what, points, weights):
+        """the checked points [B,N,3] and weights [B,N] or None of fit_points and nearest_vertices, contiguous"""
+        _need_gpu(what, points, *(() if weights is None else (weights,)))
+        _check_model(what, self.model, points)
+        if points.dim() != 3 or points.shape[0] == 0 or not 1 <= points.shape[1] <= POINTS_MAX_N or points.shape[2] != 3 \
+                or points.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 points [B,N,3] with B >= 1 and N in 1..{POINTS_MAX_N}, got {points.dtype} "
+                            f"{tuple(points.shape)}")
+        B, N = points.shape[0], points.shape[1]
+        if weights is not None and (tuple(weights.shape) != (B, N) or weights.dtype != torch.float32):
+            raise ScatError(f"{what} needs fp32 weights [{B},{N}], got {weights.dtype} {tuple(weights.shape)}")
+        return points.contiguous(), None if weights is None else weights.contiguous()
+
+    def fit_points(self, points, init, weights=None, rounds=5, iters=4, max_dist=None, free=ALL_FREE):
+        """points [B,N,3] fp32, an unordered cloud with N <= 8192 -> PointFitResult.  Nearest-vertex ICP: `rounds` times
+        {every point to its nearest model vertex; `iters` Levenberg-Marquardt iterations of fit_vertices on the
+        per-vertex centroids}, then one more assignment that the result's idx, dist, matched, data_cost and rms describe.
+        init: the start, required, p [B,62] or any fit result (it is not modified; of a KeypointFitResult the first 62):
+        ICP is local and finds the hand only from nearby, a joints fit of the same hand is the natural start.
+        weights: [B,N] or None (all ones); a point of weight 0 does not count.  max_dist: points farther than this from
+        the model do not count in a round (a hard trim, in the points' unit); None keeps all.  free: bit i clear freezes
+        unknown i.  rounds in 1..64, rounds x iters <= 256.  A hand with a point, weight or start that is not finite, or
+        a negative weight, is not fitted: data_cost +inf, accepted 0, p the start; a hand with nothing matched keeps its
+        p too."""
+        what = "ManoFitter.fit_points"
+        if init is None:
+            raise ScatError(f"{what} needs a start: p [B,62] or a fit result")
+        points, weights = self._cloud(what, points, weights)
+        B = points.shape[0]
+        if isinstance(init, KeypointFitResult):
+            init = init.p[:, :UNKNOWNS]
+        p = _start(what, init, FitResult, B, UNKNOWNS, points.device)
+        rounds, iters = int(rounds), int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
+            raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
+                            f"{POINTS_MAX_STEPS} steps")
+        cost, accepted, idx, dist, stats = mano_fit_points(self.model, points, weights, p, rounds, iters, _max_dist(what, max_dist),
+                                                           self.lambda0, self.w_pose, self.w_beta, free)
+        mw = stats[:, 1]
+        rms = torch.where(mw > 0, (stats[:, 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
+        return PointFitResult(*_groups(p), cost, accepted, p, stats[:, 2].long(), rms, idx, dist)
+
+    def nearest_vertices(self, result_or_verts, points, weights=None, max_dist=None):
+        """-> Correspondences of the cloud points [B,N,3] with the model at a fit result or p [B,62] (the vertices are
+        posed inside the launch) or with the caller's vertices [B,V,3] (any V <= 1536): per point the nearest vertex and its distance,
+        per vertex the weight and centroid of its matched points, which are fit_vertices' weights and targets."""
+        what = "ManoFitter.nearest_vertices"
+        points, weights = self._cloud(what, points, weights)
+        B, d = points.shape[0], _max_dist(what, max_dist)
+        if isinstance(result_or_verts, torch.Tensor) and result_or_verts.dim() != 2:
+            verts = result_or_verts
+            _need_gpu(what, verts)
+            if verts.dim() != 3 or verts.shape[0] != B or not 1 <= verts.shape[1] <= MAX_V or verts.shape[2] != 3 \
+                    or verts.dtype != torch.float32 or verts.device != points.device:
+                raise ScatError(f"{what} needs fp32 verts [{B},V,3] with V in 1..{MAX_V} on {points.device}, got "
+                                f"{verts.dtype} {tuple(verts.shape)} on {verts.device}")
+            return cloud_assign(verts.contiguous(), points, weights, d)
+        r = result_or_verts
+        p = r.p[:, :UNKNOWNS] if isinstance(r, KeypointFitResult) else r if isinstance(r, torch.Tensor) else getattr(r, "p", None)
+        if not isinstance(p, torch.Tensor) or tuple(p.shape) != (B, UNKNOWNS) or p.dtype != torch.float32:
+            raise ScatError(f"{what} needs a fit result or fp32 p [{B},{UNKNOWNS}], or fp32 verts [{B},V,3]")
+        _need_gpu(what, p)
+        return mano_cloud_assign(self.model, p.contiguous(), points, weights, d)
 
     def fit_mesh_outputs(self, out, weights=None):
         """out [B,21+V,3]: joints and mesh in the layout of ManoLayer / scat_mano_fwd; the V vertex rows are fitted"""
