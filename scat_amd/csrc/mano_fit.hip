@@ -1,18 +1,19 @@
 // The inverse of the MANO layer, include/scat_mano_fit.h: the 21 joints with their analytic Jacobian, and a
 // Levenberg-Marquardt fit of pose, shape and a similarity to 21 target joints.  One workgroup of 256 threads per sample.
 //
-// jac_eval is what both kernels share.  After mano_setup (mano_common.h) it needs no pass over the mesh: the blend rows
-// and skinning weights of the five tip vertices are copied into LDS once per workgroup (jac_load_model), a tip is blended
-// and skinned from there in mano_vertex's order, and the Jacobian is forward mode, one (joint, column) pair per
-// work-item.  With y_i the un-rotated joints (t_i of the chain, v' of a tip), x_j = Rg (y_j - y_1):
+// jac_eval (mano_fit_common.h) is what the joints kernels share.  After mano_setup (mano_common.h) it needs no pass over
+// the mesh: the blend rows and skinning weights of the five tip vertices are copied into LDS once per workgroup
+// (jac_load_model), a tip is blended and skinned from there in mano_vertex's order, and the Jacobian is forward mode, one
+// (joint, column) pair per work-item.  With y_i the un-rotated joints (t_i of the chain, v' of a tip), x_j = Rg (y_j - y_1):
 //   rots m        dRg/dr_m (y_j - y_1)
 //   pose (k, m)   RG_i = RG_parent(k) R_k (...), so d RG_i = Omega RG_i and d t_i = Omega (t_i - t_k) for i in k's subtree,
 //                 Omega = RG_parent(k) dR_k/dr_m RG_k^T; a tip adds T (posedirs_k . dR_k/dr_m) through v_posed
 //   beta b        d t_i = d J_0 + sum over the path of RG_parent (dJ_c - dJ_parent), a tip
 //                 sum_i w_i (RG_i (shapedirs_b - dJ_i) + d t_i)
 // mano_fit_kernel keeps J (63 x 62), the normal matrix with g as its 63rd row, and both parameter vectors in LDS.  The
-// factorisation, the back substitution, the accept step and the final write are mano_fit_common.h's lm_solve, lm_accept,
-// lm_commit and lm_write, described there.  All sums are sequential loops in a fixed order.
+// residuals and the cost (fit_residual, fit_cost), the factorisation, the back substitution, the accept step and the final
+// write (lm_solve, lm_accept, lm_commit, lm_write) are mano_fit_common.h's, described there; the walk that assembles the
+// normal equations is the kernel's.  All sums are sequential loops in a fixed order.
 #include "mano_fit_common.h"
 
 namespace scat {
@@ -52,30 +53,6 @@ struct FitLds {
     float cost, lambda;
     int acc, bad, fail, take;
 };
-
-// residuals of the model joints m.x under the similarity of pp; with_cols: the four similarity columns of J as well
-__device__ __forceinline__ void fit_residual(const JacLds& m, FitLds& f, const float* pp, bool with_cols) {
-    const int row = threadIdx.x;
-    if (row < kFRows) {
-        const int c = row % 3;
-        const float sx = expf(pp[kFU - 1]) * m.x[row];
-        f.r[row] = (sx + pp[kFModel + c]) - f.tgt[row];
-        if (with_cols) {
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc) f.J[row][kFModel + cc] = cc == c ? 1.f : 0.f;
-            f.J[row][kFU - 1] = sx;
-        }
-    }
-}
-
-// one thread, ascending: the joints, then the priors
-__device__ __forceinline__ float fit_cost(const FitLds& f, const float* pp, float w_pose, float w_beta) {
-    float c = 0.f, sp = 0.f, sb = 0.f;
-    for (int row = 0; row < kFRows; ++row) c += f.w[row / 3] * (f.r[row] * f.r[row]);
-    for (int i = 3; i < 3 + kFPose; ++i) sp += pp[i] * pp[i];
-    for (int i = 3 + kFPose; i < kFModel; ++i) sb += pp[i] * pp[i];
-    return c + (w_pose * sp + w_beta * sb);
-}
 
 // grid = B, block = 256
 __global__ __launch_bounds__(kFThreads) void mano_fit_kernel(FitArgs a) {
@@ -188,10 +165,8 @@ extern "C" int scat_mano_fit(const float* blend, const float* joint_t, const flo
                  targets, weights, joint_map, p, cost, accepted, iters, init, lambda0, w_pose, w_beta, free_mask};
     int rc = mano_validate(fn, ptrs, 10, B, V, parents, tips, &a.m.levels);
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(((uintptr_t)weights & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
-    rc = fit_check_args(fn, "Procrustes", iters, init, lambda0, w_pose, w_beta);
+    rc = fit_check_args(fn, "Procrustes", weights, iters, init, lambda0, w_pose, w_beta, free_mask);
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
     hipLaunchKernelGGL(mano_fit_kernel, dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
     SCAT_LAUNCH_CHECK(fn);
     set_kernel_label("mano_fit_v%d_i%d", V, iters);

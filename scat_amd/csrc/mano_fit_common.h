@@ -1,9 +1,13 @@
-// What the two fit kernels share (mano_fit.hip: 3-D joints, quadratic; mano_fit_kp.hip: 2-D keypoints, robust loss, joint
-// limits): the constants, the LDS state of the joints' Jacobian with jac_load_model and jac_eval, the Procrustes start with
-// fit_axis_angle, fit_finite, the steps of the solver that do not depend on the problem (lm_solve, lm_accept, lm_commit,
-// lm_write) and the entry points' shared argument handling.  mano_fit.hip's header comment has the derivation of the
-// Jacobian's columns.  What stays in each kernel is what its problem decides: staging, the usable-inputs test, the start,
-// residuals and cost, and the walk that assembles the normal equations, whose row sums compile well only in the kernel.
+// What the fit kernels share (mano_fit.hip: 3-D joints, quadratic; mano_fit_kp.hip: 2-D keypoints, robust loss, joint
+// limits; mano_fit_seq.hip: a track of frames; mano_fit_verts.hip: a full mesh; mano_fit_points.hip: a point cloud): the
+// constants, the LDS state of the joints' Jacobian with jac_load_model and jac_eval, the usable-inputs scan over global
+// memory (fit_unusable), the Procrustes start with fit_axis_angle, fit_finite, the quadratic joints problem's residuals and
+// cost (fit_residual, fit_cost), the steps of the solver that do not depend on the problem (lm_factor, lm_backsub, lm_solve,
+// lm_decide, lm_accept, lm_commit, lm_write) and the entry points' shared argument handling.  mano_fit.hip's header
+// comment has the derivation of the Jacobian's columns.  What stays in each kernel is what its problem decides: staging,
+// the start, the robust or per-vertex residuals and cost, and the walk that assembles the normal equations, whose row sums
+// compile well only in the kernel.  The mesh kernel (mano_fit_verts.hip) keeps all of its device code, its scan included
+// (DESIGN.md 13 has why).
 #pragma once
 #include "mano_common.h"
 
@@ -285,6 +289,18 @@ __device__ void jac_eval(JacLds& m, const ManoArgs& p, int64_t b, bool want_jac,
 
 __device__ __forceinline__ bool fit_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
+// This thread's share of the usable-inputs scan: nonzero if one of the nx values is not finite, or one of the nw weights
+// (w may be null) is not finite or negative.  The caller ORs over the workgroup with __syncthreads_or
+__device__ __forceinline__ int fit_unusable(const float* x, int nx, const float* w, int nw) {
+    const int tid = threadIdx.x;
+    int bad = 0;
+    for (int i = tid; i < nx; i += kFThreads) bad |= !fit_finite(x[i]);
+    if (w) {
+        for (int i = tid; i < nw; i += kFThreads) bad |= !(fit_finite(w[i]) && w[i] >= 0.f);
+    }
+    return bad;
+}
+
 // The rotation matrix R as an axis-angle r: R -> unit quaternion by the largest of the four candidates, w >= 0, then
 // r = 2 atan2(|v|, w) v / |v|
 __device__ void fit_axis_angle(const double* R, float* r) {
@@ -347,13 +363,41 @@ __device__ void fit_procrustes(const float* x, const float* y, const float* w, f
     p[kFU - 1] = (float)log(sc);
 }
 
+// The quadratic joints problem (mano_fit.hip, mano_fit_seq.hip) on a kernel's LDS state f with J, r, tgt and w: the
+// residuals of the model joints m.x under the similarity of pp; with_cols: the four similarity columns of J as well
+template <class F>
+__device__ __forceinline__ void fit_residual(const JacLds& m, F& f, const float* pp, bool with_cols) {
+    const int row = threadIdx.x;
+    if (row < kFRows) {
+        const int c = row % 3;
+        const float sx = expf(pp[kFU - 1]) * m.x[row];
+        f.r[row] = (sx + pp[kFModel + c]) - f.tgt[row];
+        if (with_cols) {
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) f.J[row][kFModel + cc] = cc == c ? 1.f : 0.f;
+            f.J[row][kFU - 1] = sx;
+        }
+    }
+}
+
+// one thread, ascending: the joints, then the priors
+template <class F>
+__device__ __forceinline__ float fit_cost(const F& f, const float* pp, float w_pose, float w_beta) {
+    float c = 0.f, sp = 0.f, sb = 0.f;
+    for (int row = 0; row < kFRows; ++row) c += f.w[row / 3] * (f.r[row] * f.r[row]);
+    for (int i = 3; i < 3 + kFPose; ++i) sp += pp[i] * pp[i];
+    for (int i = 3 + kFPose; i < kFModel; ++i) sb += pp[i] * pp[i];
+    return c + (w_pose * sp + w_beta * sb);
+}
+
 // The steps of Levenberg-Marquardt that do not depend on the problem, on a kernel's LDS state f: A[N + 1][N] (lower
 // triangle: the damped normal matrix, g as row N), col[N + 1], delta, p, pt[N], cost, lambda, acc, fail, take.
 //
-// A left-looking Cholesky, one thread per row, two barriers per column; row N (g) rides along and ends as L^-1 g.  Then
-// L^T x = L^-1 g by columns, last first, one barrier per column; delta = -x.
+// lm_factor: a left-looking Cholesky, one thread per row, two barriers per column; row N (g) rides along and ends as
+// L^-1 g.  lm_backsub: L^T x = L^-1 g by columns, last first, one barrier per column; delta = -x.  lm_solve is the two; the
+// sequence kernel changes the right-hand side between them.
 template <int N, class F>
-__device__ __forceinline__ void lm_solve(F& f) {
+__device__ __forceinline__ void lm_factor(F& f) {
     const int tid = threadIdx.x;
     for (int k = 0; k < N; ++k) {
         if (tid >= k && tid <= N) {
@@ -371,11 +415,34 @@ __device__ __forceinline__ void lm_solve(F& f) {
         else if (tid > k && tid <= N) f.A[tid][k] = f.col[tid] / l;
         __syncthreads();
     }
+}
+
+template <int N, class F>
+__device__ __forceinline__ void lm_backsub(F& f) {
+    const int tid = threadIdx.x;
     for (int k = N - 1; k >= 0; --k) {
         const float xk = f.A[N][k] / f.A[k][k];
         if (tid < k) f.A[N][tid] -= f.A[k][tid] * xk;
         else if (tid == k) f.delta[k] = -xk;
         __syncthreads();
+    }
+}
+
+template <int N, class F>
+__device__ __forceinline__ void lm_solve(F& f) {
+    lm_factor<N>(f);
+    lm_backsub<N>(f);
+}
+
+// One thread: the step with the cost ct is taken (ok) or not; cost, acc and the schedule of lambda
+template <class F>
+__device__ __forceinline__ void lm_decide(F& f, bool ok, float ct) {
+    if (ok) {
+        f.cost = ct;
+        f.acc += 1;
+        f.lambda = fmaxf(f.lambda * 0.1f, kFLambdaMin);
+    } else {
+        f.lambda = fminf(f.lambda * 10.f, kFLambdaMax);
     }
 }
 
@@ -385,13 +452,7 @@ __device__ __forceinline__ void lm_accept(F& f, float ct) {
     bool ok = !f.fail && ct < f.cost;
     for (int i = 0; i < N; ++i) ok = ok && fit_finite(f.pt[i]);
     f.take = ok;
-    if (ok) {
-        f.cost = ct;
-        f.acc += 1;
-        f.lambda = fmaxf(f.lambda * 0.1f, kFLambdaMin);
-    } else {
-        f.lambda = fminf(f.lambda * 10.f, kFLambdaMax);
-    }
+    lm_decide(f, ok, ct);
 }
 
 // All threads, after lm_accept
@@ -422,9 +483,20 @@ static scat::ManoArgs fit_model_args(const float* blend, const float* joint_t, c
             {{tips[0], tips[1], tips[2], tips[3], tips[4]}}};
 }
 
-// The checks that every fit's entry point makes at the same place (free_mask's comes later in scat_mano_fit_kp, and stays
-// there); start: what it calls its closed-form start
-static int fit_check_args(const char* fn, const char* start, int iters, int init, float lambda0, float w_pose, float w_beta) {
+// the mesh and cloud kernels read no tip: vertex 0 stands in for the five, which every V >= 1 has
+static const int kNoTips[scat::kMTips] = {0, 0, 0, 0, 0};
+
+// The checks that the fits' entry points share, each text in one place.  fit_check_args is the three in a row, as
+// scat_mano_fit and scat_mano_fit_verts make them; an entry point with checks of its own between them (the frames and the
+// smoothness weights of scat_mano_fit_seq, the steps of scat_mano_fit_points, the camera of scat_mano_fit_kp) calls the
+// parts in its order.  weights may be null; mano_validate has seen the pointers that may not be
+static int fit_check_weights(const char* fn, const float* weights) {
+    SCAT_REQUIRE(((uintptr_t)weights & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
+    return SCAT_OK;
+}
+
+// start: what the entry point calls its closed-form start
+static int fit_check_solver(const char* fn, const char* start, int iters, int init, float lambda0, float w_pose, float w_beta) {
     using namespace scat;
     SCAT_REQUIRE(iters >= 1 && iters <= SCAT_FIT_MAX_ITERS, SCAT_E_ARG, "%s: %d iterations outside 1..%d", fn, iters,
                  SCAT_FIT_MAX_ITERS);
@@ -434,4 +506,17 @@ static int fit_check_args(const char* fn, const char* start, int iters, int init
     SCAT_REQUIRE(w_pose >= 0.f && w_pose < INFINITY, SCAT_E_ARG, "%s: w_pose %g must be finite and not negative", fn, (double)w_pose);
     SCAT_REQUIRE(w_beta >= 0.f && w_beta < INFINITY, SCAT_E_ARG, "%s: w_beta %g must be finite and not negative", fn, (double)w_beta);
     return SCAT_OK;
+}
+
+static int fit_check_mask(const char* fn, uint64_t free_mask) {
+    SCAT_REQUIRE((free_mask >> scat::kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, scat::kFU - 1);
+    return SCAT_OK;
+}
+
+static int fit_check_args(const char* fn, const char* start, const float* weights, int iters, int init, float lambda0,
+                          float w_pose, float w_beta, uint64_t free_mask) {
+    int rc = fit_check_weights(fn, weights);
+    if (rc == SCAT_OK) rc = fit_check_solver(fn, start, iters, init, lambda0, w_pose, w_beta);
+    if (rc == SCAT_OK) rc = fit_check_mask(fn, free_mask);
+    return rc;
 }

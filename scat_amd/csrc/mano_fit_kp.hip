@@ -406,14 +406,15 @@ extern "C" int scat_mano_fit_kp(const float* blend, const float* joint_t, const 
     SCAT_REQUIRE(targets3 || !weights3, SCAT_E_ARG, "%s: weights3 given without targets3", fn);
     SCAT_REQUIRE(targets2 || !weights2, SCAT_E_ARG, "%s: weights2 given without targets2", fn);
     SCAT_REQUIRE(!pose_lo == !pose_hi, SCAT_E_ARG, "%s: pose_lo and pose_hi must both be given or both be null", fn);
-    rc = fit_check_args(fn, "the closed-form start", iters, init, lambda0, w_pose, w_beta);
+    rc = fit_check_solver(fn, "the closed-form start", iters, init, lambda0, w_pose, w_beta);
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(kp_weight_ok(w_limit), SCAT_E_ARG, "%s: w_limit %g must be finite and not negative", fn, (double)w_limit);
     SCAT_REQUIRE(kp_weight_ok(sigma3), SCAT_E_ARG, "%s: sigma3 %g must be finite and not negative", fn, (double)sigma3);
     SCAT_REQUIRE(kp_weight_ok(sigma2), SCAT_E_ARG, "%s: sigma2 %g must be finite and not negative", fn, (double)sigma2);
     SCAT_REQUIRE(half_w > 0.f && half_w < INFINITY, SCAT_E_ARG, "%s: half_w %g must be positive and finite", fn, (double)half_w);
     SCAT_REQUIRE(half_h > 0.f && half_h < INFINITY, SCAT_E_ARG, "%s: half_h %g must be positive and finite", fn, (double)half_h);
-    SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
+    rc = fit_check_mask(fn, free_mask);
+    if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(free_cam >= 0 && free_cam <= 7, SCAT_E_ARG, "%s: free_cam %d outside 0..7", fn, free_cam);
     hipLaunchKernelGGL(mano_fit_kp_kernel, dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
     SCAT_LAUNCH_CHECK(fn);

@@ -13,6 +13,7 @@
 //                  ascending (four indices per LDS read), adding w, w q and w d2 of its points in fp64 (d2 recomputed by the walk's expression: the
 //                  same bits).  The three totals of stats: each thread's vertices ascending, an xor butterfly over the
 //                  wavefront, the four wavefronts ascending.
+// The usable-inputs scan of the points and their weights is mano_fit_common.h's fit_unusable.
 // Static LDS at the largest sizes: 18 KiB of vertices, 32 KiB of indices, 2.6 KiB of pose state: 53 KiB of the 64.
 // scat_mano_fit_points launches {assign, scat_mano_fit_verts} `rounds` times and one last assign; each assign after the
 // first adds the accepted count of the fit before it to the caller's total.
@@ -114,11 +115,7 @@ __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
     const float* wts = a.weights ? a.weights + b * (int64_t)N : nullptr;
     if (tid == 0 && a.fold) a.acc_total[b] = a.fold == 1 ? 0 : a.acc_total[b] + a.acc_round[b];
 
-    int bad = 0;
-    for (int i = tid; i < 3 * N; i += kFThreads) bad |= !fit_finite(pts[i]);
-    if (wts) {
-        for (int i = tid; i < N; i += kFThreads) bad |= !(fit_finite(wts[i]) && wts[i] >= 0.f);
-    }
+    int bad = fit_unusable(pts, 3 * N, wts, N);
     if constexpr (kParams) {
         if (tid < kFU) {
             const float v = a.p[b * kFU + tid];
@@ -263,8 +260,6 @@ __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
 
 using namespace scat;
 
-static const int kNoTips[kMTips] = {0, 0, 0, 0, 0};
-
 // what the three entry points check alike, after the pointers that must not be null
 static int cloud_check(const char* fn, const void* const* nullable, int nn, const double* stats, int N, float max_dist) {
     uintptr_t all = 0;
@@ -371,11 +366,12 @@ extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, co
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(rounds >= 1 && rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, rounds,
                  SCAT_FIT_POINTS_MAX_ROUNDS);
-    rc = fit_check_args(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
+    rc = fit_check_solver(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(rounds * iters <= SCAT_FIT_POINTS_MAX_STEPS, SCAT_E_ARG, "%s: %d rounds of %d iterations are more than %d steps",
                  fn, rounds, iters, SCAT_FIT_POINTS_MAX_STEPS);
-    SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
+    rc = fit_check_mask(fn, free_mask);
+    if (rc != SCAT_OK) return rc;
     const PointsWs w = points_ws(B, N, V);
     SCAT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "%s: the workspace must be a 16-byte-aligned pointer", fn);
     SCAT_REQUIRE(ws_bytes >= w.total, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,

@@ -1,13 +1,15 @@
 // The MANO fit to a track of frames, include/scat_mano_fit_seq.h: mano_fit.hip's problem over T frames of one sequence,
 // coupled by a quadratic penalty on consecutive unknowns, as one Levenberg-Marquardt.  One workgroup of 256 threads per
-// sequence walks the frames in order, all iterations in one launch.
+// sequence walks the frames in order, all iterations in one launch.  The frame's residuals and cost (fit_residual,
+// fit_cost), the two halves of the solve (lm_factor, lm_backsub), the accept step's decision (lm_decide) and the
+// usable-inputs scan (fit_unusable, each thread's share) are mano_fit_common.h's; the block-tridiagonal elimination is this kernel's.
 //
 // The damped normal matrix is block-tridiagonal: H_t (62 x 62) on the diagonal, -D beside it.  It is factored exactly,
 // frame by frame (the header has the recurrences).  Per frame, J, A_t and g_t are built in LDS by mano_fit.hip's walk,
 // with the smoothness on the diagonal and in g.  Then
 //   rank update   M_t^T, which the frame before left in the workspace, is read into the LDS that J occupied (J is dead
 //                 once A_t and g_t stand); H_t -= M_t M_t^T over the lower triangle with all threads, g_t -= M_t y_t-1
-//   factor        lm_factor: lm_solve's left-looking Cholesky, g riding along as row 62 and ending as y_t
+//   factor        lm_factor: the left-looking Cholesky of lm_solve, g riding along as row 62 and ending as y_t
 //   M_t+1^T       = -L_t^-1 D: 62 forward substitutions, one thread per column, the column written to and read back from
 //                 LDS by its own thread only, so no barrier.  It is lower triangular (L^-1 is), which the rank update
 //                 and the backward pass use.
@@ -62,68 +64,9 @@ __device__ __forceinline__ float seq_weight(const SeqArgs& a, int i) {
     return i < 3 ? a.s_rots : i < 3 + kFPose ? a.s_poses : i < kFModel ? a.s_betas : i < kFU - 1 ? a.s_trans : a.s_scale;
 }
 
-// lm_solve's two halves, for a system whose right-hand side changes between them.  The factor: a left-looking Cholesky,
-// one thread per row, two barriers per column; row N rides along and ends as L^-1 (row N).
-template <int N, class F>
-__device__ __forceinline__ void lm_factor(F& f) {
-    const int tid = threadIdx.x;
-    for (int k = 0; k < N; ++k) {
-        if (tid >= k && tid <= N) {
-            float s = f.A[tid][k];
-            for (int j = 0; j < k; ++j) s -= f.A[tid][j] * f.A[k][j];
-            f.col[tid] = s;
-        }
-        __syncthreads();
-        const float d = f.col[k];
-        if (!(d > 0.f) || !fit_finite(d)) {
-            if (tid == 0) f.fail = 1;
-        }
-        const float l = sqrtf(d);
-        if (tid == k) f.A[k][k] = l;
-        else if (tid > k && tid <= N) f.A[tid][k] = f.col[tid] / l;
-        __syncthreads();
-    }
-}
-
-// L^T x = row N by columns, last first, one barrier per column; delta = -x
-template <int N, class F>
-__device__ __forceinline__ void lm_backsub(F& f) {
-    const int tid = threadIdx.x;
-    for (int k = N - 1; k >= 0; --k) {
-        const float xk = f.A[N][k] / f.A[k][k];
-        if (tid < k) f.A[N][tid] -= f.A[k][tid] * xk;
-        else if (tid == k) f.delta[k] = -xk;
-        __syncthreads();
-    }
-}
-
-// mano_fit.hip's residuals and cost on this kernel's LDS state
-__device__ __forceinline__ void seq_residual(const JacLds& m, SeqLds& f, const float* pp, bool with_cols) {
-    const int row = threadIdx.x;
-    if (row < kFRows) {
-        const int c = row % 3;
-        const float sx = expf(pp[kFU - 1]) * m.x[row];
-        f.r[row] = (sx + pp[kFModel + c]) - f.tgt[row];
-        if (with_cols) {
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc) f.J[row][kFModel + cc] = cc == c ? 1.f : 0.f;
-            f.J[row][kFU - 1] = sx;
-        }
-    }
-}
-
-// one thread, ascending: the joints, then the priors
-__device__ __forceinline__ float seq_frame_cost(const SeqLds& f, const float* pp, float w_pose, float w_beta) {
-    float c = 0.f, sp = 0.f, sb = 0.f;
-    for (int row = 0; row < kFRows; ++row) c += f.w[row / 3] * (f.r[row] * f.r[row]);
-    for (int i = 3; i < 3 + kFPose; ++i) sp += pp[i] * pp[i];
-    for (int i = 3 + kFPose; i < kFModel; ++i) sb += pp[i] * pp[i];
-    return c + (w_pose * sp + w_beta * sb);
-}
-
 // one thread: frame t's terms of the cost onto the running sums, q the frame's unknowns and qp those of the frame before
 __device__ __forceinline__ void seq_cost_add(SeqLds& f, const float* q, const float* qp, int t, float w_pose, float w_beta) {
-    f.cd += seq_frame_cost(f, q, w_pose, w_beta);
+    f.cd += fit_cost(f, q, w_pose, w_beta);
     if (t > 0) {
         float cs = f.cs;
         for (int i = 0; i < kFU; ++i) {
@@ -220,16 +163,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kernel(SeqArgs a) {
         f.cost = INFINITY;
     }
     __syncthreads();
-    {   // usable inputs: every target and weight of every frame
-        int bad = 0;
-        for (int i = tid; i < T * kFRows; i += kFThreads) bad |= !fit_finite(tg[i]);
-        if (wt)
-            for (int i = tid; i < T * kFJoints; i += kFThreads) {
-                const float w = wt[i];
-                bad |= !(fit_finite(w) && w >= 0.f);
-            }
-        if (bad) f.bad = 1;
-    }
+    if (fit_unusable(tg, T * kFRows, wt, T * kFJoints)) f.bad = 1;   // usable inputs: every target and weight of every frame
     __syncthreads();
     if (f.bad) {   // the same for every thread of the workgroup
         if (a.init)
@@ -275,7 +209,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kernel(SeqArgs a) {
             seq_stage(f, tg, wt, P, f.p, t, T);
             __syncthreads();
             jac_eval(m, pc, 0, true, expf(f.p[kFU - 1]), &f.J[0][0], kFU);
-            seq_residual(m, f, f.p, true);
+            fit_residual(m, f, f.p, true);
             __syncthreads();
             if (tid == 0) seq_cost_add(f, f.p, f.pp, t, a.w_pose, a.w_beta);
             // A_t = J^T W J + priors + c_t D (lower triangle), g_t as row 62; a frozen unknown is a unit row
@@ -372,7 +306,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kernel(SeqArgs a) {
             seq_stage(f, tg, wt, Q, f.pt, t, T);
             __syncthreads();
             jac_eval(m, pt, 0, false, 1.f, nullptr, 0);
-            seq_residual(m, f, f.pt, false);
+            fit_residual(m, f, f.pt, false);
             __syncthreads();
             if (tid == 0) {
                 seq_cost_add(f, f.pt, f.pp, t, a.w_pose, a.w_beta);
@@ -385,14 +319,8 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kernel(SeqArgs a) {
         if (tid == 0) {   // taken if every pivot was positive, every trial unknown is finite and the cost drops
             const float c = f.cd + f.cs;
             const bool ok = !f.fail && f.fin && c < f.cost;
-            if (ok) {
-                f.cost = c;
-                f.acc += 1;
-                f.cur ^= 1;
-                f.lambda = fmaxf(f.lambda * 0.1f, kFLambdaMin);
-            } else {
-                f.lambda = fminf(f.lambda * 10.f, kFLambdaMax);
-            }
+            lm_decide(f, ok, c);
+            if (ok) f.cur ^= 1;   // the buffers swap roles, where lm_commit copies pt
         }
     }
     __syncthreads();
@@ -429,16 +357,18 @@ extern "C" int scat_mano_fit_seq(const float* blend, const float* joint_t, const
                  s_rots, s_poses, s_betas, s_trans, s_scale, free_mask};
     int rc = mano_validate(fn, ptrs, 10, S, V, parents, tips, &a.m.levels);
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(((uintptr_t)weights & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
+    rc = fit_check_weights(fn, weights);
+    if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(T >= 1 && T <= kSMaxT, SCAT_E_SHAPE, "%s: %d frames outside 1..%d", fn, T, kSMaxT);
-    rc = fit_check_args(fn, "Procrustes, frame by frame", iters, init, lambda0, w_pose, w_beta);
+    rc = fit_check_solver(fn, "Procrustes, frame by frame", iters, init, lambda0, w_pose, w_beta);
     if (rc != SCAT_OK) return rc;
     const float sw[5] = {s_rots, s_poses, s_betas, s_trans, s_scale};
     const char* const sn[5] = {"s_rots", "s_poses", "s_betas", "s_trans", "s_scale"};
     for (int i = 0; i < 5; ++i)
         SCAT_REQUIRE(sw[i] >= 0.f && sw[i] < INFINITY, SCAT_E_ARG, "%s: %s %g must be finite and not negative", fn, sn[i],
                      (double)sw[i]);
-    SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
+    rc = fit_check_mask(fn, free_mask);
+    if (rc != SCAT_OK) return rc;
     const int64_t need = scat_mano_fit_seq_ws(S, T);
     SCAT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "%s: the workspace must be a 16-byte-aligned pointer", fn);
     SCAT_REQUIRE(ws_bytes >= need, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,

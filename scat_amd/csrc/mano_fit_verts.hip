@@ -586,9 +586,6 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
 
 using namespace scat;
 
-// the kernels here read no tip: vertex 0 stands in for the five, which every V >= 1 has
-static const int kNoTips[kMTips] = {0, 0, 0, 0, 0};
-
 extern "C" int scat_mano_verts_jac(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
                                    const float* hands_mean, const float* rots, const float* poses, const float* betas,
                                    float* verts, float* jac, int B, int V, uint64_t parents, void* stream) {
@@ -613,10 +610,8 @@ static int fit_verts_launch(const char* fn, const float* blend, const float* joi
                   targets, weights, p, cost, accepted, iters, init, lambda0, w_pose, w_beta, free_mask};
     int rc = mano_validate(fn, ptrs, 9, B, V, parents, kNoTips, &a.m.levels);
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(((uintptr_t)weights & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
-    rc = fit_check_args(fn, "Procrustes over the vertices", iters, init, lambda0, w_pose, w_beta);
+    rc = fit_check_args(fn, "Procrustes over the vertices", weights, iters, init, lambda0, w_pose, w_beta, free_mask);
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE((free_mask >> kFU) == 0, SCAT_E_ARG, "%s: free_mask has bits above %d set", fn, kFU - 1);
     const dim3 grid(B), block(kFThreads);
     if (tile == kVTile) {
         hipLaunchKernelGGL(mano_fit_verts_kernel<kVTile>, grid, block, 0, (hipStream_t)stream, a);

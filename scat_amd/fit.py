@@ -35,6 +35,7 @@ scanner's: nearest-vertex ICP from the caller's start, every round one assignmen
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
+import math
 import os
 from typing import NamedTuple
 
@@ -134,15 +135,44 @@ def _check_model(what, model, ref):
         raise ScatError(f"{what}: the model is on {model.device}, the inputs on {ref.device}: call ManoModel.to first")
 
 
-def _start(what, init, result_type, B, unknowns, device):
-    """the p [B,unknowns] a kernel reads and writes: empty for init None, else a checked copy of init (tensor or result)"""
+def _start(what, init, result_types, shape, device):
+    """the p of `shape` a kernel reads and writes: empty for init None, else a checked copy of init (a tensor, or the p of a
+    result of one of result_types)"""
     if init is None:
-        return torch.empty((B, unknowns), dtype=torch.float32, device=device)
-    p0 = init.p if isinstance(init, (result_type, PointFitResult)) else init
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    p0 = init.p if isinstance(init, result_types) else init
     _need_gpu(what, p0)
-    if tuple(p0.shape) != (B, unknowns) or p0.dtype != torch.float32:
-        raise ScatError(f"{what} needs an fp32 start [{B},{unknowns}], got {p0.dtype} {tuple(p0.shape)}")
+    if tuple(p0.shape) != tuple(shape) or p0.dtype != torch.float32:
+        raise ScatError(f"{what} needs an fp32 start [{','.join(str(n) for n in shape)}], got {p0.dtype} {tuple(p0.shape)}")
     return p0.clone().contiguous()
+
+
+def _weights(what, weights, shape):
+    """the checked weights of `shape`, contiguous, or None"""
+    if weights is None:
+        return None
+    if tuple(weights.shape) != tuple(shape) or weights.dtype != torch.float32:
+        raise ScatError(f"{what} needs fp32 weights [{','.join(str(n) for n in shape)}], got {weights.dtype} "
+                        f"{tuple(weights.shape)}")
+    return weights.contiguous()
+
+
+def _results(n, device):
+    """cost [n] and accepted [n] int32 for a kernel to write"""
+    return torch.empty((n,), dtype=torch.float32, device=device), torch.empty((n,), dtype=torch.int32, device=device)
+
+
+def _model_inputs(what, model, rots, poses, betas):
+    """the checked rots [B,3], poses [B,45], betas [B,10] of a Jacobian's entry point, contiguous, and B"""
+    _need_gpu(what, rots, poses, betas)
+    _check_model(what, model, rots)
+    B = rots.shape[0]
+    if B == 0 or tuple(rots.shape) != (B, 3) or tuple(poses.shape) != (B, POSE) or tuple(betas.shape) != (B, BETAS):
+        raise ScatError(f"{what} needs rots [B,3], poses [B,45], betas [B,10] with B >= 1, got {tuple(rots.shape)}, "
+                        f"{tuple(poses.shape)}, {tuple(betas.shape)}")
+    if not all(t.dtype == torch.float32 for t in (rots, poses, betas)):
+        raise ScatError(f"{what} needs fp32 tensors")
+    return rots.contiguous(), poses.contiguous(), betas.contiguous(), B
 
 
 def _check_ranges(what, iters, masks_ok, and_cam=""):
@@ -154,8 +184,6 @@ def _check_ranges(what, iters, masks_ok, and_cam=""):
 
 def _smooth(what, smooth):
     """the five smoothness weights in the entry point's order, from a dict with keys among SMOOTH_KEYS"""
-    import math
-
     smooth = {} if smooth is None else dict(smooth)
     unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
     if unknown:
@@ -169,20 +197,12 @@ def _smooth(what, smooth):
 
 def _groups(p):
     """rots, poses, betas, trans, scale: the five groups every fit's p begins with"""
-    return p[:, 0:3], p[:, 3:48], p[:, 48:58], p[:, 58:61], torch.exp(p[:, 61])
+    return p[..., 0:3], p[..., 3:48], p[..., 48:58], p[..., 58:61], torch.exp(p[..., 61])
 
 
 def mano_joints_jac(model, rots, poses, betas):
     """-> (joints [B,21,3], jac [B,63,58]): the 21 joints of mano_fwd and d joints / d (rots, poses, betas), one launch"""
-    _need_gpu("mano_joints_jac", rots, poses, betas)
-    _check_model("mano_joints_jac", model, rots)
-    B = rots.shape[0]
-    if B == 0 or tuple(rots.shape) != (B, 3) or tuple(poses.shape) != (B, POSE) or tuple(betas.shape) != (B, BETAS):
-        raise ScatError(f"mano_joints_jac needs rots [B,3], poses [B,45], betas [B,10] with B >= 1, got {tuple(rots.shape)}, "
-                        f"{tuple(poses.shape)}, {tuple(betas.shape)}")
-    if not all(t.dtype == torch.float32 for t in (rots, poses, betas)):
-        raise ScatError("mano_joints_jac needs fp32 tensors")
-    rots, poses, betas = rots.contiguous(), poses.contiguous(), betas.contiguous()
+    rots, poses, betas, B = _model_inputs("mano_joints_jac", model, rots, poses, betas)
     joints = torch.empty((B, 21, 3), dtype=torch.float32, device=rots.device)
     jac = torch.empty((B, 63, 58), dtype=torch.float32, device=rots.device)
     lib().scat_mano_joints_jac(*_model_args(model), _p(rots), _p(poses), _p(betas), _p(joints), _p(jac), B, model.V,
@@ -194,8 +214,7 @@ def mano_fit(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose
     """scat_mano_fit as it is declared: targets [B,21,3], weights [B,21] or None, joint_map int32 [21] on the device,
     p [B,62] (read when init = 0, written) -> (cost [B], accepted [B] int32)"""
     B = targets.shape[0]
-    cost = torch.empty((B,), dtype=torch.float32, device=targets.device)
-    accepted = torch.empty((B,), dtype=torch.int32, device=targets.device)
+    cost, accepted = _results(B, targets.device)
     lib().scat_mano_fit(*_model_args(model), _p(targets), _p(weights), _p(joint_map), _p(p), _p(cost), _p(accepted), B, model.V,
                         model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose), float(w_beta),
                         int(free), _stream())
@@ -205,15 +224,7 @@ def mano_fit(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose
 def mano_verts_jac(model, rots, poses, betas):
     """-> (verts [B,V,3], jac [B,3V,58]): the mesh of mano_fwd (its rows 21..) and d verts / d (rots, poses, betas), one
     launch"""
-    _need_gpu("mano_verts_jac", rots, poses, betas)
-    _check_model("mano_verts_jac", model, rots)
-    B = rots.shape[0]
-    if B == 0 or tuple(rots.shape) != (B, 3) or tuple(poses.shape) != (B, POSE) or tuple(betas.shape) != (B, BETAS):
-        raise ScatError(f"mano_verts_jac needs rots [B,3], poses [B,45], betas [B,10] with B >= 1, got {tuple(rots.shape)}, "
-                        f"{tuple(poses.shape)}, {tuple(betas.shape)}")
-    if not all(t.dtype == torch.float32 for t in (rots, poses, betas)):
-        raise ScatError("mano_verts_jac needs fp32 tensors")
-    rots, poses, betas = rots.contiguous(), poses.contiguous(), betas.contiguous()
+    rots, poses, betas, B = _model_inputs("mano_verts_jac", model, rots, poses, betas)
     verts = torch.empty((B, model.V, 3), dtype=torch.float32, device=rots.device)
     jac = torch.empty((B, 3 * model.V, 58), dtype=torch.float32, device=rots.device)
     lib().bind(FIT_VERTS_HEADER).scat_mano_verts_jac(*_model_args(model), _p(rots), _p(poses), _p(betas), _p(verts), _p(jac), B,
@@ -225,8 +236,7 @@ def mano_fit_verts(model, targets, weights, p, iters, init, lambda0, w_pose, w_b
     """scat_mano_fit_verts as it is declared: targets [B,V,3], weights [B,V] or None, p [B,62] (read when init = 0,
     written) -> (cost [B], accepted [B] int32)"""
     B = targets.shape[0]
-    cost = torch.empty((B,), dtype=torch.float32, device=targets.device)
-    accepted = torch.empty((B,), dtype=torch.int32, device=targets.device)
+    cost, accepted = _results(B, targets.device)
     lib().bind(FIT_VERTS_HEADER).scat_mano_fit_verts(*_model_args(model), _p(targets), _p(weights), _p(p), _p(cost), _p(accepted), B,
                                                      model.V, model.parents_packed, int(iters), int(init), float(lambda0),
                                                      float(w_pose), float(w_beta), int(free), _stream())
@@ -234,8 +244,6 @@ def mano_fit_verts(model, targets, weights, p, iters, init, lambda0, w_pose, w_b
 
 
 def _max_dist(what, max_dist):
-    import math
-
     d = math.inf if max_dist is None else float(max_dist)
     if not d > 0.0:
         raise ScatError(f"{what}: max_dist {max_dist} must be positive (None: no trim)")
@@ -281,8 +289,7 @@ def mano_fit_points(model, points, weights, p, rounds, iters, max_dist, lambda0,
     workspace is allocated here, at the size scat_mano_fit_points_ws gives (0 for sizes the launch refuses)."""
     B, N = int(points.shape[0]), int(points.shape[1])
     dev = points.device
-    cost = torch.empty((B,), dtype=torch.float32, device=dev)
-    accepted = torch.empty((B,), dtype=torch.int32, device=dev)
+    cost, accepted = _results(B, dev)
     idx = torch.empty((B, N), dtype=torch.int32, device=dev)
     dist = torch.empty((B, N), dtype=torch.float32, device=dev)
     ns = lib().bind(FIT_POINTS_HEADER)
@@ -300,8 +307,7 @@ def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_l
     leaves a term out, or means all ones), joint_map int32 [21] on the device, pose_lo / pose_hi [45] or None, p [B,65]
     (read when init = 0, written) -> (cost [B], accepted [B] int32)"""
     B = p.shape[0]
-    cost = torch.empty((B,), dtype=torch.float32, device=p.device)
-    accepted = torch.empty((B,), dtype=torch.int32, device=p.device)
+    cost, accepted = _results(B, p.device)
     lib().scat_mano_fit_kp(*_model_args(model), _p(targets3), _p(weights3), _p(targets2), _p(weights2), _p(joint_map), _p(pose_lo),
                            _p(pose_hi), _p(p), _p(cost), _p(accepted), B, model.V, model.parents_packed, *model.tips, int(iters),
                            int(init), float(lambda0), float(w_pose), float(w_beta), float(w_limit), float(sigma3), float(sigma2),
@@ -315,8 +321,7 @@ def mano_fit_seq(model, targets, weights, joint_map, p, iters, init, lambda0, w_
     device, p [S,T,62] (read when init = 0, written) -> (cost [S], accepted [S] int32).  The workspace is allocated here,
     at the size scat_mano_fit_seq_ws gives (0 for sizes the launch refuses)."""
     S, T = int(targets.shape[0]), int(targets.shape[1])
-    cost = torch.empty((S,), dtype=torch.float32, device=targets.device)
-    accepted = torch.empty((S,), dtype=torch.int32, device=targets.device)
+    cost, accepted = _results(S, targets.device)
     L = lib()
     nbytes = int(L.scat_mano_fit_seq_ws(S, T))
     ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=targets.device)
@@ -355,14 +360,12 @@ class ManoFitter:
         B = joints.shape[0]
         if B == 0 or tuple(joints.shape) != (B, 21, 3) or joints.dtype != torch.float32:
             raise ScatError(f"ManoFitter.fit needs fp32 joints [B,21,3] with B >= 1, got {joints.dtype} {tuple(joints.shape)}")
-        if weights is not None and (tuple(weights.shape) != (B, 21) or weights.dtype != torch.float32):
-            raise ScatError(f"ManoFitter.fit needs fp32 weights [{B},21], got {weights.dtype} {tuple(weights.shape)}")
-        p = _start("ManoFitter.fit", init, FitResult, B, UNKNOWNS, joints.device)
+        weights = _weights("ManoFitter.fit", weights, (B, 21))
+        p = _start("ManoFitter.fit", init, (FitResult, PointFitResult), (B, UNKNOWNS), joints.device)
         iters = self.iters if iters is None else int(iters)
         _check_ranges("ManoFitter.fit", iters, 0 <= int(free) <= ALL_FREE)
-        cost, accepted = mano_fit(self.model, joints.contiguous(), None if weights is None else weights.contiguous(),
-                                  self._map_on(joints.device), p, iters, 0 if init is not None else 1,
-                                  self.lambda0, self.w_pose, self.w_beta, free)
+        cost, accepted = mano_fit(self.model, joints.contiguous(), weights, self._map_on(joints.device), p, iters,
+                                  0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, free)
         return FitResult(*_groups(p), cost, accepted, p)
 
     def _map_on(self, device):
@@ -391,13 +394,12 @@ class ManoFitter:
         B, V = verts.shape[0], self.model.V
         if B == 0 or tuple(verts.shape) != (B, V, 3) or verts.dtype != torch.float32:
             raise ScatError(f"{what} needs fp32 verts [B,{V},3] with B >= 1, got {verts.dtype} {tuple(verts.shape)}")
-        if weights is not None and (tuple(weights.shape) != (B, V) or weights.dtype != torch.float32):
-            raise ScatError(f"{what} needs fp32 weights [{B},{V}], got {weights.dtype} {tuple(weights.shape)}")
-        p = _start(what, init, FitResult, B, UNKNOWNS, verts.device)
+        weights = _weights(what, weights, (B, V))
+        p = _start(what, init, (FitResult, PointFitResult), (B, UNKNOWNS), verts.device)
         iters = self.iters if iters is None else int(iters)
         _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
-        cost, accepted = mano_fit_verts(self.model, verts.contiguous(), None if weights is None else weights.contiguous(), p,
-                                        iters, 0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, free)
+        cost, accepted = mano_fit_verts(self.model, verts.contiguous(), weights, p, iters, 0 if init is not None else 1,
+                                        self.lambda0, self.w_pose, self.w_beta, free)
         return FitResult(*_groups(p), cost, accepted, p)
 
     def _cloud(self, what, points, weights):
@@ -408,10 +410,7 @@ class ManoFitter:
                 or points.dtype != torch.float32:
             raise ScatError(f"{what} needs fp32 points [B,N,3] with B >= 1 and N in 1..{POINTS_MAX_N}, got {points.dtype} "
                             f"{tuple(points.shape)}")
-        B, N = points.shape[0], points.shape[1]
-        if weights is not None and (tuple(weights.shape) != (B, N) or weights.dtype != torch.float32):
-            raise ScatError(f"{what} needs fp32 weights [{B},{N}], got {weights.dtype} {tuple(weights.shape)}")
-        return points.contiguous(), None if weights is None else weights.contiguous()
+        return points.contiguous(), _weights(what, weights, tuple(points.shape[:2]))
 
     def fit_points(self, points, init, weights=None, rounds=5, iters=4, max_dist=None, free=ALL_FREE):
         """points [B,N,3] fp32, an unordered cloud with N <= 8192 -> PointFitResult.  Nearest-vertex ICP: `rounds` times
@@ -431,7 +430,7 @@ class ManoFitter:
         B = points.shape[0]
         if isinstance(init, KeypointFitResult):
             init = init.p[:, :UNKNOWNS]
-        p = _start(what, init, FitResult, B, UNKNOWNS, points.device)
+        p = _start(what, init, (FitResult, PointFitResult), (B, UNKNOWNS), points.device)
         rounds, iters = int(rounds), int(iters)
         _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
         if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
@@ -495,22 +494,13 @@ class ManoFitter:
             raise ScatError(f"{what} needs fp32 joints [S,T,21,3] with S >= 1 and T in 1..{SEQ_MAX_T}, got {joints.dtype} "
                             f"{tuple(joints.shape)}")
         S, T = int(joints.shape[0]), int(joints.shape[1])
-        if weights is not None and (tuple(weights.shape) != (S, T, 21) or weights.dtype != torch.float32):
-            raise ScatError(f"{what} needs fp32 weights [{S},{T},21], got {weights.dtype} {tuple(weights.shape)}")
-        if init is None:
-            p = torch.empty((S, T, UNKNOWNS), dtype=torch.float32, device=joints.device)
-        else:
-            p0 = init.p if isinstance(init, SequenceFitResult) else init
-            _need_gpu(what, p0)
-            if tuple(p0.shape) != (S, T, UNKNOWNS) or p0.dtype != torch.float32:
-                raise ScatError(f"{what} needs an fp32 start [{S},{T},{UNKNOWNS}], got {p0.dtype} {tuple(p0.shape)}")
-            p = p0.clone().contiguous()
+        weights = _weights(what, weights, (S, T, 21))
+        p = _start(what, init, SequenceFitResult, (S, T, UNKNOWNS), joints.device)
         iters = self.iters if iters is None else int(iters)
         _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
-        cost, accepted = mano_fit_seq(self.model, joints.contiguous(), None if weights is None else weights.contiguous(),
-                                      self._map_on(joints.device), p, iters, 0 if init is not None else 1, self.lambda0,
-                                      self.w_pose, self.w_beta, *sm, free)
-        return SequenceFitResult(p[..., 0:3], p[..., 3:48], p[..., 48:58], p[..., 58:61], torch.exp(p[..., 61]), cost, accepted, p)
+        cost, accepted = mano_fit_seq(self.model, joints.contiguous(), weights, self._map_on(joints.device), p, iters,
+                                      0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, *sm, free)
+        return SequenceFitResult(*_groups(p), cost, accepted, p)
 
     def fit_outputs_sequence(self, out66, weights=None, smooth=None):
         """out66 [S,T,66]: the network's camera and 21 root-relative joints for every frame of S tracks; the joints are
@@ -556,7 +546,7 @@ class ManoFitter:
         H, W = (float(v) for v in size)
         if not (H > 0 and W > 0):
             raise ScatError(f"{what}: size {size} must be positive")
-        p = _start(what, init, KeypointFitResult, B, KP_UNKNOWNS, ref.device)
+        p = _start(what, init, (KeypointFitResult, PointFitResult), (B, KP_UNKNOWNS), ref.device)
         iters = self.iters if iters is None else int(iters)
         if free is None:
             free = ALL_FREE if joints3d is not None else free_mask(trans=False, log_scale=False)

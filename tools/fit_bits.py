@@ -1,0 +1,112 @@
+#!/usr/bin/env python
+"""A SHA-256 of every output tensor of every fit entry point, through scat_amd.fit, on the inputs of tests/_fit*_cases.py:
+the bits that a change to the fit kernels which is to compute the same thing must keep.  Run it once with the library to
+compare against (SCAT_LIBPATH) and once with this tree's, each in its own process, and diff the two outputs
+(profiles/fit_family_refactor.txt is such a pair).
+
+The smallest shapes: V = 37, and 778 once per entry point; 6 hands for the joints, keypoint and mesh fits, 2 sequences of 5
+frames, a cloud of (3, 257, 37).  5 iterations; the closed-form start and the caller's; one run with a frozen group and one
+with some zero weights."""
+import hashlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+ITERS = 5
+
+
+def main():
+    import _fit_kp_cases as KC
+    import _fit_points_cases as PC
+    import _fit_seq_cases as SC
+    import _fit_verts_cases as VC
+    from _fit_cases import JOINT_MAP, host_model
+    from scat_amd import synth
+    from scat_amd._lib import lib
+    from scat_amd.fit import ManoFitter, free_mask, mano_joints_jac, mano_verts_jac
+
+    lib().scat_check_device()
+    dev = torch.device("cuda", 0)
+
+    def show(name, res):
+        fields = res._asdict().items() if hasattr(res, "_asdict") else enumerate(res)
+        for k, t in fields:
+            t = t.detach().cpu().contiguous()
+            print(f"{name}.{k} {t.dtype} {list(t.shape)} {hashlib.sha256(t.numpy().tobytes()).hexdigest()}")
+
+    frozen = free_mask(betas=False, log_scale=False)
+    for V in (37, 778):
+        fitter = ManoFitter(host_model(V).to(dev), joint_map=JOINT_MAP, iters=ITERS)
+        P, Tj, Tv = VC.seeded(V)
+        P, Tj, Tv = P.float().to(dev), Tj.float().to(dev), Tv.to(dev)
+        near = KC.near_start(V)[:, :62].float().to(dev)       # 0.05 off the truth in the 58 model unknowns
+        wj = torch.ones(6, 21, device=dev)
+        wj[:, ::4] = 0.0
+        wj[:, 1] = 0.5
+        wv = torch.ones(6, V, device=dev)
+        wv[:, ::3] = 0.0
+        wv[:, 1::3] = 0.25
+
+        show(f"v{V}.joints_jac", mano_joints_jac(fitter.model, P[:, 0:3], P[:, 3:48], P[:, 48:58]))
+        show(f"v{V}.fit", fitter.fit(Tj))
+        show(f"v{V}.fit.init", fitter.fit(Tj, init=near))
+        show(f"v{V}.fit.frozen", fitter.fit(Tj, init=near, free=frozen))
+        show(f"v{V}.fit.weights", fitter.fit(Tj, weights=wj))
+
+        _, T3, T2 = KC.truth(V)
+        T3, T2 = T3.to(dev), T2.to(dev)
+        near65 = KC.near_start(V).float().to(dev)
+        w2 = torch.full((6, 21), KC.W2, device=dev)
+        show(f"v{V}.kp.3d", fitter.fit_keypoints(joints3d=T3, free_cam=0))
+        show(f"v{V}.kp.both", fitter.fit_keypoints(joints3d=T3, joints2d=T2, w2=w2))
+        show(f"v{V}.kp.both.init", fitter.fit_keypoints(joints3d=T3, joints2d=T2, w2=w2, init=near65, sigma3=0.01, sigma2=10.0))
+        show(f"v{V}.kp.2d", fitter.fit_keypoints(joints2d=T2))
+        show(f"v{V}.kp.frozen", fitter.fit_keypoints(joints3d=T3, joints2d=T2, w2=w2, init=near65, free=frozen))
+        show(f"v{V}.kp.weights", fitter.fit_keypoints(joints3d=T3, joints2d=T2, w3=wj, w2=w2 * wj))
+
+        Ps, X = SC.track(25, 2, 5, V)
+        X = X.to(dev)
+        off = 0.05 * torch.from_numpy(np.array(synth.normal_like(23, "seq.off", (2, 5, 58), 1.0))).float()
+        near_s = Ps.float().clone()
+        near_s[:, :, :58] += off
+        near_s = near_s.to(dev)
+        ws = torch.ones(2, 5, 21, device=dev)
+        ws[:, 2] = 0.0                                           # a frame without data, bridged by its neighbours
+        ws[:, :, 3] = 0.0
+        show(f"v{V}.seq", fitter.fit_sequence(X, smooth=SC.SMOOTH))
+        show(f"v{V}.seq.decoupled", fitter.fit_sequence(X))
+        show(f"v{V}.seq.init", fitter.fit_sequence(X, smooth=SC.SMOOTH, init=near_s))
+        show(f"v{V}.seq.frozen", fitter.fit_sequence(X, smooth=SC.SMOOTH, init=near_s, free=frozen))
+        show(f"v{V}.seq.weights", fitter.fit_sequence(X, weights=ws, smooth=SC.SMOOTH))
+
+        show(f"v{V}.verts_jac", mano_verts_jac(fitter.model, P[:, 0:3], P[:, 3:48], P[:, 48:58]))
+        show(f"v{V}.verts", fitter.fit_vertices(Tv))
+        show(f"v{V}.verts.init", fitter.fit_vertices(Tv, init=near))
+        show(f"v{V}.verts.frozen", fitter.fit_vertices(Tv, init=near, free=frozen))
+        show(f"v{V}.verts.weights", fitter.fit_vertices(Tv, weights=wv))
+
+        if V == 37:      # the random cloud of the assignment tests; for the model's forms 257 points 3 mm off the hands' meshes
+            verts, cloud, weights, cloud_dist, _ = PC.assign_case(3, 257, 37, True)
+            verts, cloud, weights = (torch.from_numpy(np.array(t)).to(dev) for t in (verts, cloud, weights))
+            noise = torch.from_numpy(np.array(synth.normal_like(29, "bits.noise", (3, 257, 3), 0.003))).float().to(dev)
+            points = (Tv[:3, torch.arange(257, device=dev) * 7 % V] + noise).contiguous()
+            max_dist, start = 0.02, near[:3].contiguous()      # the start is centimetres off: both sides of the trim are taken
+        else:            # the hands' own meshes as unordered clouds
+            points, weights, max_dist, start = torch.from_numpy(np.array(PC.cloud(V, "shuffled"))).to(dev), None, PC.TRIM, near
+            verts, cloud, cloud_dist = Tv, points, max_dist
+        show(f"v{V}.nearest.verts", fitter.nearest_vertices(verts, cloud, weights, cloud_dist))
+        show(f"v{V}.nearest.p", fitter.nearest_vertices(start, points, weights, max_dist))
+        show(f"v{V}.points", fitter.fit_points(points, start, rounds=3, iters=ITERS))
+        show(f"v{V}.points.trim", fitter.fit_points(points, start, weights=weights, rounds=3, iters=ITERS, max_dist=max_dist))
+        show(f"v{V}.points.frozen", fitter.fit_points(points, start, weights=weights, rounds=2, iters=ITERS, free=frozen))
+    torch.cuda.synchronize()
+
+
+if __name__ == "__main__":
+    main()
