@@ -1,13 +1,14 @@
 // What the fit kernels share (mano_fit.hip: 3-D joints, quadratic; mano_fit_kp.hip: 2-D keypoints, robust loss, joint
-// limits; mano_fit_seq.hip: a track of frames; mano_fit_verts.hip: a full mesh; mano_fit_points.hip: a point cloud): the
-// constants, the LDS state of the joints' Jacobian with jac_load_model and jac_eval, the usable-inputs scan over global
-// memory (fit_unusable), the Procrustes start with fit_axis_angle, fit_finite, the quadratic joints problem's residuals and
-// cost (fit_residual, fit_cost), the steps of the solver that do not depend on the problem (lm_factor, lm_backsub, lm_solve,
+// limits; mano_fit_seq.hip: a track of frames; mano_fit_seq_kp.hip: a track of keypoints; mano_fit_verts.hip: a full mesh;
+// mano_fit_points.hip: a point cloud): the constants, the LDS state of the joints' Jacobian with jac_load_model and
+// jac_eval, the usable-inputs scan over global memory (fit_unusable), the Procrustes start with fit_axis_angle, the track
+// kernels' scan over the frames' starts (fit_start_scan), fit_finite, the quadratic joints problem's residuals and cost
+// (fit_residual, fit_cost), the steps of the solver that do not depend on the problem (lm_factor, lm_backsub, lm_solve,
 // lm_decide, lm_accept, lm_commit, lm_write) and the entry points' shared argument handling.  mano_fit.hip's header
 // comment has the derivation of the Jacobian's columns.  What stays in each kernel is what its problem decides: staging,
 // the start, the robust or per-vertex residuals and cost, and the walk that assembles the normal equations, whose row sums
-// compile well only in the kernel.  The mesh kernel (mano_fit_verts.hip) keeps all of its device code, its scan included
-// (DESIGN.md 13 has why).
+// compile well only in the kernel; what the two keypoint kernels share of that is mano_fit_kp_common.h's.  The mesh kernel
+// (mano_fit_verts.hip) keeps all of its device code, its scan included (DESIGN.md 13 has why).
 #pragma once
 #include "mano_common.h"
 
@@ -361,6 +362,45 @@ __device__ void fit_procrustes(const float* x, const float* y, const float* w, f
     for (int c = 0; c < 3; ++c)
         p[kFModel + c] = (float)(my[c] - sc * (R[3 * c] * mx[0] + R[3 * c + 1] * mx[1] + R[3 * c + 2] * mx[2]));
     p[kFU - 1] = (float)log(sc);
+}
+
+// init = 1 of the track kernels (mano_fit_seq.hip, mano_fit_seq_kp.hip), one thread, after every frame's own start in
+// P[T][N]: a frame without weight (has[t] == 0) takes the rots and what follows the model unknowns (the similarity, and the
+// camera where N has one) of the frame before it, frame 0 those of the first frame that has weight; and rots_t takes the
+// equivalent axis-angle that is closer to rots_t-1
+template <int N>
+__device__ void fit_start_scan(const unsigned char* has, float* P, int T) {
+    int first = -1;
+    for (int t = 0; t < T && first < 0; ++t)
+        if (has[t]) first = t;
+    if (first < 0) return;   // every start is the identity similarity: zeros
+    for (int t = 0; t < T; ++t) {
+        float* q = P + t * N;
+        if (!has[t]) {
+            const float* src = P + (t > 0 ? t - 1 : first) * N;
+            for (int i = 0; i < 3; ++i) q[i] = src[i];
+            for (int i = kFModel; i < N; ++i) q[i] = src[i];
+        } else if (t > 0) {
+            const float* pr = q - N;
+            double r[3], n2 = 0.0;
+            for (int c = 0; c < 3; ++c) {
+                r[c] = q[c];
+                n2 += r[c] * r[c];
+            }
+            const double n = sqrt(n2);
+            if (n > 0.0) {
+                const double k = 1.0 - 6.283185307179586477 / n;
+                double da = 0.0, db = 0.0;
+                for (int c = 0; c < 3; ++c) {
+                    const double ea = r[c] * k - pr[c], eb = r[c] - pr[c];
+                    da += ea * ea;
+                    db += eb * eb;
+                }
+                if (da < db)
+                    for (int c = 0; c < 3; ++c) q[c] = (float)(r[c] * k);
+            }
+        }
+    }
 }
 
 // The quadratic joints problem (mano_fit.hip, mano_fit_seq.hip) on a kernel's LDS state f with J, r, tgt and w: the

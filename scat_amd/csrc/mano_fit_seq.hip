@@ -2,7 +2,8 @@
 // coupled by a quadratic penalty on consecutive unknowns, as one Levenberg-Marquardt.  One workgroup of 256 threads per
 // sequence walks the frames in order, all iterations in one launch.  The frame's residuals and cost (fit_residual,
 // fit_cost), the two halves of the solve (lm_factor, lm_backsub), the accept step's decision (lm_decide) and the
-// usable-inputs scan (fit_unusable, each thread's share) are mano_fit_common.h's; the block-tridiagonal elimination is this kernel's.
+// usable-inputs scan (fit_unusable, each thread's share) and the scan over the frames' starts (fit_start_scan) are
+// mano_fit_common.h's; the block-tridiagonal elimination is this kernel's.
 //
 // The damped normal matrix is block-tridiagonal: H_t (62 x 62) on the diagonal, -D beside it.  It is factored exactly,
 // frame by frame (the header has the recurrences).  Per frame, J, A_t and g_t are built in LDS by mano_fit.hip's walk,
@@ -93,42 +94,6 @@ __device__ __forceinline__ void seq_stage(SeqLds& f, const float* tg, const floa
     }
 }
 
-// init = 1, one thread, after every frame's own Procrustes: frames without weight take their neighbour's start, and
-// rots_t takes the equivalent axis-angle that is closer to rots_t-1
-__device__ void seq_start_scan(const SeqLds& f, float* P, int T) {
-    int first = -1;
-    for (int t = 0; t < T && first < 0; ++t)
-        if (f.has[t]) first = t;
-    if (first < 0) return;   // every start is the identity similarity: zeros
-    for (int t = 0; t < T; ++t) {
-        float* q = P + t * kFU;
-        if (!f.has[t]) {
-            const float* src = P + (t > 0 ? t - 1 : first) * kFU;
-            for (int i = 0; i < 3; ++i) q[i] = src[i];
-            for (int i = kFModel; i < kFU; ++i) q[i] = src[i];
-        } else if (t > 0) {
-            const float* pr = q - kFU;
-            double r[3], n2 = 0.0;
-            for (int c = 0; c < 3; ++c) {
-                r[c] = q[c];
-                n2 += r[c] * r[c];
-            }
-            const double n = sqrt(n2);
-            if (n > 0.0) {
-                const double k = 1.0 - 6.283185307179586477 / n;
-                double da = 0.0, db = 0.0;
-                for (int c = 0; c < 3; ++c) {
-                    const double ea = r[c] * k - pr[c], eb = r[c] - pr[c];
-                    da += ea * ea;
-                    db += eb * eb;
-                }
-                if (da < db)
-                    for (int c = 0; c < 3; ++c) q[c] = (float)(r[c] * k);
-            }
-        }
-    }
-}
-
 // grid = S, block = 256
 __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kernel(SeqArgs a) {
     __shared__ JacLds m;
@@ -191,7 +156,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kernel(SeqArgs a) {
             fit_procrustes(m.x, tg + tid * kFRows, w, q);
         }
         __syncthreads();
-        if (tid == 0) seq_start_scan(f, wp, T);
+        if (tid == 0) fit_start_scan<kFU>(f.has, wp, T);
     } else {
         for (int i = tid; i < np; i += kFThreads) wp[i] = pg[i];
     }

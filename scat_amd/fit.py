@@ -20,6 +20,13 @@ without data:
     res = fitter.fit_sequence(joints, smooth=dict(rots=1e-4, poses=1e-4, betas=1e-2, trans=1e-1, scale=1e-1))
     verts = fitter.mesh(res)                           # [S,T,V,3]
 
+fit_keypoints_sequence (include/scat_mano_fit_seq_kp.h, csrc/mano_fit_seq_kp.hip) is the two together, what video needs:
+a track of 2-D keypoints (and / or 3-D joints) with outliers and gaps, the camera among the unknowns, one solve per track:
+
+    res = fitter.fit_keypoints_sequence(joints2d=kp, sigma2=10.0,      # from 2-D alone the data term is in pixels squared
+                                        smooth=dict(rots=6e3, poses=2e3, betas=2e4, cam_scale=1e3, cam_trans=4e5))
+    frames = renderer.render(fitter.mesh(res).flatten(0, 1), res.cam.flatten(0, 1))
+
 fit_vertices (include/scat_mano_fit_verts.h, csrc/mano_fit_verts.hip) takes a mesh in the model's topology, which decides
 the twist and the shape that 21 joints leave open; a joints fit of the same hand is its natural warm start:
 
@@ -51,10 +58,14 @@ ALL_FREE = (1 << UNKNOWNS) - 1
 KP_UNKNOWNS = 65               # the 62, then the camera cs, ctx, cty: SCAT_FIT_KP_UNKNOWNS
 SEQ_MAX_T = 256                # SCAT_FIT_SEQ_MAX_T
 SMOOTH_KEYS = ("rots", "poses", "betas", "trans", "scale")      # s_rots .. s_scale, in the entry point's order
+# s_rots .. s_ct of scat_mano_fit_seq_kp, in the entry point's order: the five, then the camera's scale and its offsets
+SMOOTH_KP_KEYS = SMOOTH_KEYS + ("cam_scale", "cam_trans")
 # bound on first use by lib().bind, beside _lib.py's tables: the MANO fit to a full mesh
 FIT_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_verts.h")
 # likewise: the MANO fit to a point cloud
 FIT_POINTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_points.h")
+# likewise: the MANO fit to a track of keypoints
+FIT_SEQ_KP_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_seq_kp.h")
 POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
 POINTS_MAX_ROUNDS = 64         # SCAT_FIT_POINTS_MAX_ROUNDS
 POINTS_MAX_STEPS = 256         # SCAT_FIT_POINTS_MAX_STEPS: rounds * iters
@@ -103,6 +114,18 @@ class SequenceFitResult(NamedTuple):
     cost: torch.Tensor       # [S], +inf for a sequence with a target or weight that was not finite
     accepted: torch.Tensor   # [S] int32
     p: torch.Tensor          # [S,T,62]: the five groups as the kernel holds them (log_scale last)
+
+
+class KeypointSequenceFitResult(NamedTuple):
+    rots: torch.Tensor       # [S,T,3]
+    poses: torch.Tensor      # [S,T,45]
+    betas: torch.Tensor      # [S,T,10]
+    trans: torch.Tensor      # [S,T,3]
+    scale: torch.Tensor      # [S,T]
+    cam: torch.Tensor        # [S,T,3]: (s, tx, ty) per frame, the camera of project_outputs and MeshRenderer.render
+    cost: torch.Tensor       # [S], +inf for a sequence with a target or weight that was not finite
+    accepted: torch.Tensor   # [S] int32
+    p: torch.Tensor          # [S,T,65]: the six groups as the kernel holds them (log_scale, then the camera, last)
 
 
 class Correspondences(NamedTuple):
@@ -182,14 +205,14 @@ def _check_ranges(what, iters, masks_ok, and_cam=""):
         raise ScatError(f"{what}: free has bits above {UNKNOWNS - 1} set{and_cam}")
 
 
-def _smooth(what, smooth):
-    """the five smoothness weights in the entry point's order, from a dict with keys among SMOOTH_KEYS"""
+def _smooth(what, smooth, keys=SMOOTH_KEYS):
+    """the smoothness weights in the entry point's order, from a dict with keys among `keys`"""
     smooth = {} if smooth is None else dict(smooth)
-    unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
+    unknown = sorted(set(smooth) - set(keys))
     if unknown:
-        raise ScatError(f"{what}: unknown smooth keys {unknown}, the groups are {list(SMOOTH_KEYS)}")
-    out = tuple(float(smooth.get(k, 0.0)) for k in SMOOTH_KEYS)
-    for k, v in zip(SMOOTH_KEYS, out):
+        raise ScatError(f"{what}: unknown smooth keys {unknown}, the groups are {list(keys)}")
+    out = tuple(float(smooth.get(k, 0.0)) for k in keys)
+    for k, v in zip(keys, out):
         if not (math.isfinite(v) and v >= 0.0):
             raise ScatError(f"{what}: smooth[{k!r}] = {v} must be finite and not negative")
     return out
@@ -329,6 +352,26 @@ def mano_fit_seq(model, targets, weights, joint_map, p, iters, init, lambda0, w_
                         T, model.V, model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose),
                         float(w_beta), float(s_rots), float(s_poses), float(s_betas), float(s_trans), float(s_scale), int(free),
                         _stream())
+    return cost, accepted
+
+
+def mano_fit_seq_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
+                    w_beta, w_limit, sigma3, sigma2, half_w, half_h, smooth7, free=ALL_FREE, free_cam=7):
+    """scat_mano_fit_seq_kp as it is declared: targets3 [S,T,21,3] / weights3 [S,T,21], targets2 [S,T,21,2] / weights2
+    [S,T,21] (None leaves a term out, or means all ones), joint_map int32 [21] on the device, pose_lo / pose_hi [45] or
+    None, p [S,T,65] (read when init = 0, written), smooth7 = (s_rots, s_poses, s_betas, s_trans, s_scale, s_cs, s_ct)
+    -> (cost [S], accepted [S] int32).  The workspace is allocated here, at the size scat_mano_fit_seq_kp_ws gives (0 for
+    sizes the launch refuses)."""
+    S, T = int(p.shape[0]), int(p.shape[1])
+    cost, accepted = _results(S, p.device)
+    ns = lib().bind(FIT_SEQ_KP_HEADER)
+    nbytes = int(ns.scat_mano_fit_seq_kp_ws(S, T))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=p.device)
+    ns.scat_mano_fit_seq_kp(*_model_args(model), _p(targets3), _p(weights3), _p(targets2), _p(weights2), _p(joint_map), _p(pose_lo),
+                            _p(pose_hi), _p(p), _p(cost), _p(accepted), _p(ws), nbytes, S, T, model.V, model.parents_packed,
+                            *model.tips, int(iters), int(init), float(lambda0), float(w_pose), float(w_beta), float(w_limit),
+                            float(sigma3), float(sigma2), float(half_w), float(half_h), *(float(v) for v in smooth7), int(free),
+                            int(free_cam), _stream())
     return cost, accepted
 
 
@@ -559,29 +602,94 @@ class ManoFitter:
                                      0.5 * W, 0.5 * H, free, int(free_cam) if joints2d is not None else 0)
         return KeypointFitResult(*_groups(p), p[:, 62:65], cost, accepted, p)
 
+    def fit_keypoints_sequence(self, joints3d=None, joints2d=None, w3=None, w2=None, size=(224, 224), sigma3=0.0, sigma2=0.0,
+                               limits=None, w_limit=0.0, smooth=None, init=None, free=None, free_cam=7, iters=None):
+        """joints3d [S,T,21,3] and / or joints2d [S,T,21,2] (pixels of a frame of size = (H, W)), S tracks of T <= 256
+        frames -> KeypointSequenceFitResult.  fit_keypoints' problem in every frame (w3, w2 [S,T,21] or None; sigma3, sigma2,
+        limits, w_limit, size, free, free_cam as there, the same for every frame) and fit_sequence's coupling between
+        consecutive frames, solved as one Levenberg-Marquardt per track: one lambda, one accept / reject.
+        smooth: dict(rots=, poses=, betas=, trans=, scale=, cam_scale=, cam_trans=), the weight d of each group in
+        sum_i d_i (p_t,i - p_t-1,i)^2; a key left out is 0.  UNITS: as in fit_sequence each weight multiplies a squared
+        difference in the unknown's own unit: radians squared for rots and poses (the penalty is on the axis-angle numbers),
+        the joints' unit for trans, a log-ratio for scale; cam_scale is on the camera's s, a pure number, and cam_trans on
+        tx, ty, in the joints' unit.  The data term they are weighed against is in the joints' unit squared where joints3d is
+        given (w2 = 1e-6 makes a pixel count like a millimetre) and in pixels squared from joints2d alone, where weights
+        about (cs W / 2)^2 times larger do the same.  A constant shape over the track is a large betas; there is no hard constraint.
+        A frame whose weights are all zero (w2 and w3) is legal whatever its finite keypoints: it has no data term and is
+        bridged by its neighbours, which is how an occluded hand and a padded clip are passed.
+        init: None for fit_keypoints' closed-form start frame by frame, made continuous in rots (a zero-weight frame takes
+        its neighbour's); from 2-D alone each frame picks its own mirror candidate, which is not revisited along the track.
+        Or p [S,T,65] / a KeypointSequenceFitResult (it is not modified).
+        free: bit i clear freezes unknown i < 62 in every frame; None frees everything, or everything but trans and
+        log_scale when joints3d is None.  free_cam: bits 0, 1, 2 free cs, ctx, cty; without joints2d the camera stays
+        frozen.  A sequence with a keypoint or weight that is not finite, or a negative weight, in any frame is not
+        fitted: cost +inf, accepted 0, p its start."""
+        what = "ManoFitter.fit_keypoints_sequence"
+        sm = _smooth(what, smooth, SMOOTH_KP_KEYS)
+        if joints3d is None and joints2d is None:
+            raise ScatError(f"{what} needs joints3d, joints2d or both")
+        given = [t for t in (joints3d, joints2d, w3, w2) if t is not None]
+        _need_gpu(what, *given)
+        ref = joints3d if joints3d is not None else joints2d
+        _check_model(what, self.model, ref)
+        if ref.dim() != 4 or ref.shape[0] == 0 or not 1 <= ref.shape[1] <= SEQ_MAX_T:
+            raise ScatError(f"{what} needs fp32 joints3d [S,T,21,3] and / or joints2d [S,T,21,2] with S >= 1 and T in "
+                            f"1..{SEQ_MAX_T}, got {tuple(ref.shape)}")
+        S, T = int(ref.shape[0]), int(ref.shape[1])
+        for name, t, shape in (("joints3d", joints3d, (S, T, 21, 3)), ("joints2d", joints2d, (S, T, 21, 2)), ("w3", w3, (S, T, 21)),
+                               ("w2", w2, (S, T, 21))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != ref.device):
+                raise ScatError(f"{what} needs fp32 {name} {list(shape)} on {ref.device}, got {t.dtype} {tuple(t.shape)} on "
+                                f"{t.device}")
+        if (w3 is not None and joints3d is None) or (w2 is not None and joints2d is None):
+            raise ScatError(f"{what}: weights given without their joints")
+        lo = hi = None
+        if limits is not None:
+            lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(ref.device).contiguous() for t in limits)
+            if tuple(lo.shape) != (POSE,) or tuple(hi.shape) != (POSE,):
+                raise ScatError(f"{what} needs limits (lo[45], hi[45]), got {tuple(lo.shape)}, {tuple(hi.shape)}")
+        H, W = (float(v) for v in size)
+        if not (H > 0 and W > 0):
+            raise ScatError(f"{what}: size {size} must be positive")
+        p = _start(what, init, KeypointSequenceFitResult, (S, T, KP_UNKNOWNS), ref.device)
+        iters = self.iters if iters is None else int(iters)
+        if free is None:
+            free = ALL_FREE if joints3d is not None else free_mask(trans=False, log_scale=False)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE and 0 <= int(free_cam) <= 7, ", or free_cam is outside 0..7")
+        if min(float(sigma3), float(sigma2), float(w_limit)) < 0:
+            raise ScatError(f"{what}: sigma3, sigma2 and w_limit must not be negative")
+        c = lambda t: None if t is None else t.contiguous()
+        cost, accepted = mano_fit_seq_kp(self.model, c(joints3d), c(w3), c(joints2d), c(w2), self._map_on(ref.device), lo, hi, p, iters,
+                                         0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma3,
+                                         sigma2, 0.5 * W, 0.5 * H, sm, free, int(free_cam) if joints2d is not None else 0)
+        return KeypointSequenceFitResult(*_groups(p), p[..., 62:65], cost, accepted, p)
+
     def project(self, result, size=(224, 224)):
         """the fitted joints of a KeypointFitResult through its camera -> [B,21,2] pixels of a frame of size = (H, W):
-        project_outputs on (result.cam, joints(result))"""
+        project_outputs on (result.cam, joints(result)); [S,T,21,2] for a KeypointSequenceFitResult"""
         from .render import project_outputs
 
         j = self.joints(result)
-        return project_outputs(torch.cat([result.cam, j.reshape(j.shape[0], 63)], dim=1), int(size[0]), int(size[1]))
+        lead = j.shape[:-2]
+        out = project_outputs(torch.cat([result.cam.reshape(-1, 3), j.reshape(-1, 63)], dim=1), int(size[0]), int(size[1]))
+        return out.reshape(*lead, 21, 2)
 
     def joints(self, result):
-        """the fitted joints [B,21,3] in the targets' frame and order; [S,T,21,3] for a SequenceFitResult"""
+        """the fitted joints [B,21,3] in the targets' frame and order; [S,T,21,3] for a SequenceFitResult or a
+        KeypointSequenceFitResult"""
         return self._posed(result)[0]
 
     def mesh(self, result):
         """the fitted mesh [B,V,3] in the targets' frame: scale x vertices + trans, through scat_mano_fwd; [S,T,V,3] for a
-        SequenceFitResult"""
+        SequenceFitResult or a KeypointSequenceFitResult"""
         return self._posed(result)[1]
 
     def _posed(self, r):
         _need_gpu("ManoFitter.mesh", r.p)
         _check_model("ManoFitter.mesh", self.model, r.p)
-        if isinstance(r, SequenceFitResult):      # every frame as one batch, then back to [S,T,...]
+        if isinstance(r, (SequenceFitResult, KeypointSequenceFitResult)):      # every frame as one batch, then back to [S,T,...]
             S, T = r.p.shape[:2]
-            p = r.p.reshape(S * T, UNKNOWNS)
+            p = r.p[..., :UNKNOWNS].reshape(S * T, UNKNOWNS)
             j, v = self._posed(FitResult(*_groups(p), r.cost, r.accepted, p))
             return j.reshape(S, T, 21, 3), v.reshape(S, T, -1, 3)
         out = mano_fwd(self.model, r.rots.contiguous(), r.poses.contiguous(), r.betas.contiguous())
