@@ -1,18 +1,14 @@
 // What the two launches of scat_mano_fit_seq_kp share (mano_fit_seq_kp.hip: the walk; mano_fit_seq_kp_start.hip: the frames'
-// closed-form starts): the workspace's layout and the kernels' arguments.  The two kernels are two translation units on
-// purpose: compiled in one, hipcc's inliner spends the walk's registers differently (mano_fit_seq_kp.hip has the figures).
+// closed-form starts): the kernels' arguments; the workspace's layout is mano_fit_seq_common.h's at 65 unknowns.  The two
+// kernels are two translation units on purpose: compiled in one, hipcc's inliner spends the walk's registers differently
+// (mano_fit_seq_kp.hip has the figures).
 #pragma once
 #include "mano_fit_kp_common.h"
+#include "mano_fit_seq_common.h"
 
 #include "../../include/scat_mano_fit_seq_kp.h"
 
 namespace scat {
-
-// per sequence: L_t and y_t for every frame, then M_t^T for every frame, then the unknowns, two buffers of [T][65]
-constexpr int kQL = (kKU + 1) * kKU;            // 4290 floats: L_t, y_t as row 65
-constexpr int kQM = kKU * kKU;                  // 4225 floats: M_t^T
-constexpr int kQFrame = kQL + kQM + 2 * kKU;    // 8645 floats of workspace per frame
-constexpr int kQMaxT = SCAT_FIT_SEQ_MAX_T;
 
 struct SeqKpArgs {
     ManoArgs m;   // rots / poses / betas are set by the kernel (LDS)

@@ -10,19 +10,16 @@
 //
 // What a frame is comes from mano_fit_kp_common.h: residuals and IRLS weights (kp_residual), the sums over the 105 rows
 // from the stored 63 x 62 Jacobian (kp_gram, kp_grad; the 42 2-D rows are never stored), the limits (kp_excess), the
-// frame's cost (kp_cost) and the closed-form start (kp_start).  What a track is comes from mano_fit_common.h: the two
-// halves of the solve (lm_factor, lm_backsub), the accept step's decision (lm_decide), the usable-inputs scan
-// (fit_unusable) and the scan over the frames' starts (fit_start_scan).  This kernel is mano_fit_seq_kernel's walk at 65
-// unknowns with that frame inside:
-//   forward    stage the frame, J and the residuals, A_t and g_t with the smoothness on the diagonal and in g; M_t^T, which
-//              the frame before left in the workspace, is read into the LDS that J occupied (a union: J is dead once A_t
-//              and g_t stand), H_t -= M_t M_t^T, g_t -= M_t y_t-1; lm_factor; M_t+1^T = -L_t^-1 D, one thread per column
-//   backward   x_t = L_t^-T (y_t - M_t+1^T x_t+1) by lm_backsub, the trial unknowns to the workspace
+// frame's cost (kp_cost) and the closed-form start (kp_start).  What a track is comes from mano_fit_seq_common.h, shared
+// with mano_fit_seq.hip (the workspace's layout, the elimination forward and backward, the smoothness sum, the accept step
+// with the buffer swap, the refusal and the write-out), on mano_fit_common.h's lm_factor, lm_backsub, lm_decide,
+// fit_unusable and fit_start_scan.  This kernel is that walk at 65 unknowns with that frame inside:
+//   forward    stage the frame, J and the residuals, A_t and g_t with the smoothness on the diagonal and in g;
+//              seq_eliminate: H_t -= M_t M_t^T, g_t -= M_t y_t-1; lm_factor; M_t+1^T = -L_t^-1 D
+//   backward   seq_backward: x_t = L_t^-T (y_t - M_t+1^T x_t+1) by lm_backsub, the trial unknowns to the workspace
 //   cost       a third walk evaluates the trial's robust cost
-// L_t with y_t (66 x 65) and M_t^T (65 x 65) live in the workspace, with the current and the trial unknowns, two buffers
-// that swap roles on an accepted step.  Inside a launch the workspace of a sequence is touched by its own workgroup only,
-// so __syncthreads() between a write and its read is all the ordering there is; the start kernel's writes are ordered
-// before the walk by the stream.
+// Inside a launch the workspace of a sequence is touched by its own workgroup only, so __syncthreads() between a write and
+// its read is all the ordering there is; the start kernel's writes are ordered before the walk by the stream.
 #include "mano_fit_seq_kp.h"
 
 namespace scat {
@@ -48,26 +45,13 @@ struct SeqKpLds {
     float cost, lambda;
     float cd, cs;               // the running data and smoothness sums of the walk in progress
     int acc, bad, fail, fin, cur;
-    unsigned char has[kQMaxT];  // init = 1: the frame has weight
+    unsigned char has[kSeqMaxT];  // init = 1: the frame has weight
 };
 static_assert(sizeof(JacLds) + sizeof(SeqKpLds) <= 64 * 1024, "static LDS of mano_fit_seq_kp_kernel must stay under 64 KiB");
 
 __device__ __forceinline__ float seq_kp_weight(const SeqKpArgs& a, int i) {
     return i < 3 ? a.s_rots : i < 3 + kFPose ? a.s_poses : i < kFModel ? a.s_betas : i < kFU - 1 ? a.s_trans
          : i < kFU ? a.s_scale : i == kKCam ? a.s_cs : a.s_ct;
-}
-
-// one thread: frame t's terms of the cost onto the running sums, q the frame's unknowns and qp those of the frame before
-__device__ __forceinline__ void seq_kp_cost_add(SeqKpLds& f, const SeqKpArgs& a, const float* q, const float* qp, int t) {
-    f.cd += kp_cost(f, a, q);
-    if (t > 0) {
-        float cs = f.cs;
-        for (int i = 0; i < kKU; ++i) {
-            const float e = q[i] - qp[i];
-            cs += f.dc[i] * (e * e);
-        }
-        f.cs = cs;
-    }
 }
 
 // the targets and weights of frame t (an absent term: zeros; a joint without weight is staged with a zero target), and
@@ -86,12 +70,8 @@ __device__ __forceinline__ void seq_kp_stage(SeqKpLds& f, const float* tg3, cons
         const int i = tid - 96;
         const float w = tg2 ? (wt2 ? wt2[(int64_t)t * kFJoints + i / 2] : 1.f) : 0.f;
         f.tgt2[i] = w == 0.f ? 0.f : tg2[(int64_t)t * kKRows2 + i];
-    } else if (tid >= 160 && tid < 160 + kKU) {
-        const int i = tid - 160;
-        q[i] = P[t * kKU + i];
-        f.pp[i] = t > 0 ? P[(t - 1) * kKU + i] : 0.f;
-        f.pn[i] = t < T - 1 ? P[(t + 1) * kKU + i] : 0.f;
     }
+    seq_stage_unknowns<kKU>(f, P, q, t, T, 160);
 }
 
 // the frame has weight: sum w3 + sum w2 > 0, a null weights pointer of a present term being all ones
@@ -111,9 +91,9 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_kernel(SeqKpArgs a)
     const int64_t s = blockIdx.x;
     const int tid = threadIdx.x, T = a.T;
     const bool has3 = a.targets3 != nullptr, has2 = a.targets2 != nullptr;
-    float* const wl = a.ws + s * ((int64_t)T * kQFrame);   // L_t and y_t
-    float* const wm = wl + (int64_t)T * kQL;               // M_t^T, t >= 1
-    float* const wp = wm + (int64_t)T * kQM;               // the unknowns: two buffers of [T][65]
+    float* const wl = seq_ws_l<kKU>(a.ws, s, T);   // L_t and y_t
+    float* const wm = seq_ws_m<kKU>(wl, T);        // M_t^T, t >= 1
+    float* const wp = seq_ws_p<kKU>(wm, T);        // the unknowns: two buffers of [T][65]
     const float* const tg3 = has3 ? a.targets3 + s * T * kFRows : nullptr;
     const float* const wt3 = a.weights3 ? a.weights3 + s * T * kFJoints : nullptr;
     const float* const tg2 = has2 ? a.targets2 + s * T * kKRows2 : nullptr;
@@ -150,12 +130,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_kernel(SeqKpArgs a)
     }
     __syncthreads();
     if (f.bad) {   // the same for every thread of the workgroup
-        if (a.init)
-            for (int i = tid; i < np; i += kFThreads) pg[i] = i % kKU == kKCam ? 1.f : 0.f;
-        if (tid == 0) {
-            a.cost[s] = INFINITY;
-            a.accepted[s] = 0;
-        }
+        seq_refuse<kKU>(a, s, pg, np, kKCam);   // the camera (1, 0, 0)
         return;
     }
     ManoArgs pc = a.m, pt = a.m;
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_kernel(SeqKpArgs a)
             [[clang::always_inline]] jac_eval(m, pc, 0, true, expf(f.p[kFU - 1]), &f.J[0][0], kFU);
             kp_residual(m, f, a, f.p, true);
             __syncthreads();
-            if (tid == 0) seq_kp_cost_add(f, a, f.p, f.pp, t);
+            if (tid == 0) seq_cost_add<kKU>(f, kp_cost(f, a, f.p), f.p, f.pp, t);
             // A_t = J^T W J + priors + active limits + c_t D (lower triangle), g_t as row 65; a frozen unknown is a unit row
             for (int w = tid; w < (kKU + 1) * kKU; w += kFThreads) {
                 const int ai = w / kKU, bi = w % kKU;
@@ -209,67 +184,11 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_kernel(SeqKpArgs a)
                 }
             }
             __syncthreads();
-            if (t > 0) {
-                const float* mt = wm + (int64_t)t * kQM;
-                for (int i = tid; i < kQM; i += kFThreads) (&f.M[0][0])[i] = mt[i];
-                __syncthreads();
-                // H_t -= M_t M_t^T and g_t -= M_t y_t-1; M^T[k][i] = 0 for i > k
-                for (int w = tid; w < (kKU + 1) * kKU; w += kFThreads) {
-                    const int ai = w / kKU, bi = w % kKU;
-                    if (ai == kKU) {
-                        float sum = 0.f;
-                        for (int k = bi; k < kKU; ++k) sum += f.M[k][bi] * f.yp[k];
-                        f.A[kKU][bi] -= sum;
-                    } else if (bi <= ai) {
-                        float sum = 0.f;
-                        for (int k = ai; k < kKU; ++k) sum += f.M[k][ai] * f.M[k][bi];
-                        f.A[ai][bi] -= sum;
-                    }
-                }
-                __syncthreads();
-            }
-            lm_factor<kKU>(f);
-            {
-                float* lt = wl + (int64_t)t * kQL;
-                for (int i = tid; i < kQL; i += kFThreads) lt[i] = (&f.A[0][0])[i];
-            }
-            if (tid < kKU) f.yp[tid] = f.A[kKU][tid];
-            if (t < T - 1) {
-                if (tid < kKU) {   // column tid of M_t+1^T = -L_t^-1 D
-                    const float d = f.ds[tid];
-                    for (int k = 0; k < kKU; ++k) {
-                        float sum = k == tid ? -d : 0.f;
-                        for (int j = 0; j < k; ++j) sum -= f.A[k][j] * f.M[j][tid];
-                        f.M[k][tid] = sum / f.A[k][k];
-                    }
-                }
-                __syncthreads();
-                float* mt = wm + (int64_t)(t + 1) * kQM;
-                for (int i = tid; i < kQM; i += kFThreads) mt[i] = (&f.M[0][0])[i];
-            }
-            __syncthreads();
+            seq_eliminate<kKU>(f, wl, wm, t, T);
         }
         if (tid == 0) f.cost = f.cd + f.cs;
         // backward: x_t, and the trial unknowns
-        for (int t = T - 1; t >= 0; --t) {
-            const float* lt = wl + (int64_t)t * kQL;
-            for (int i = tid; i < kQL; i += kFThreads) (&f.A[0][0])[i] = lt[i];
-            if (tid < kKU) f.p[tid] = P[t * kKU + tid];
-            __syncthreads();
-            if (t < T - 1 && tid < kKU) {
-                const float* mt = wm + (int64_t)(t + 1) * kQM + tid * kKU;
-                float sum = 0.f;
-                for (int i = 0; i <= tid; ++i) sum += mt[i] * f.xn[i];
-                f.A[kKU][tid] -= sum;
-            }
-            __syncthreads();
-            lm_backsub<kKU>(f);
-            if (tid < kKU) {
-                f.xn[tid] = -f.delta[tid];
-                Q[t * kKU + tid] = kp_free(a, tid) ? f.p[tid] + f.delta[tid] : f.p[tid];
-            }
-            __syncthreads();
-        }
+        for (int t = T - 1; t >= 0; --t) seq_backward<kKU>(f, wl, wm, P, Q, t, T, tid < kKU && kp_free(a, tid));
         // the trial's cost
         if (tid == 0) {
             f.cd = 0.f, f.cs = 0.f;
@@ -282,29 +201,17 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_kernel(SeqKpArgs a)
             kp_residual(m, f, a, f.pt, false);
             __syncthreads();
             if (tid == 0) {
-                seq_kp_cost_add(f, a, f.pt, f.pp, t);
-                int fin = f.fin;
+                seq_cost_add<kKU>(f, kp_cost(f, a, f.pt), f.pt, f.pp, t);
+                int fin = f.fin;   // written out in both kernels: DESIGN.md 18 has what lifting it did
                 for (int i = 0; i < kKU; ++i) fin &= fit_finite(f.pt[i]);
                 f.fin = fin;
             }
             __syncthreads();
         }
-        if (tid == 0) {   // taken if every pivot was positive and finite, every trial unknown is finite and the cost drops
-            const float c = f.cd + f.cs;
-            const bool ok = !f.fail && f.fin && c < f.cost;
-            lm_decide(f, ok, c);
-            if (ok) f.cur ^= 1;   // the buffers swap roles
-        }
+        if (tid == 0) seq_decide(f);
     }
     __syncthreads();
-    if (a.init || f.acc > 0) {
-        const float* P = wp + f.cur * np;
-        for (int i = tid; i < np; i += kFThreads) pg[i] = P[i];
-    }
-    if (tid == 0) {
-        a.cost[s] = fit_finite(f.cost) ? f.cost : INFINITY;   // also NaN: a start that is not finite
-        a.accepted[s] = f.acc;
-    }
+    seq_write(f, a, s, wp, pg, np);
 }
 
 }  // namespace scat
@@ -312,8 +219,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_kernel(SeqKpArgs a)
 using namespace scat;
 
 extern "C" int64_t scat_mano_fit_seq_kp_ws(int S, int T) {
-    if (S < 1 || T < 1 || T > kQMaxT) return 0;
-    return (int64_t)S * T * kQFrame * (int64_t)sizeof(float);
+    return seq_ws_bytes<kKU>(S, T);
 }
 
 extern "C" int scat_mano_fit_seq_kp(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
@@ -336,24 +242,22 @@ extern "C" int scat_mano_fit_seq_kp(const float* blend, const float* joint_t, co
     if (rc != SCAT_OK) return rc;
     rc = kp_check_terms(fn, targets3, weights3, targets2, weights2, pose_lo, pose_hi);
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(T >= 1 && T <= kQMaxT, SCAT_E_SHAPE, "%s: %d frames outside 1..%d", fn, T, kQMaxT);
+    rc = seq_check_frames(fn, T);
+    if (rc != SCAT_OK) return rc;
     rc = fit_check_solver(fn, "the closed-form start, frame by frame", iters, init, lambda0, w_pose, w_beta);
     if (rc != SCAT_OK) return rc;
     rc = kp_check_loss(fn, w_limit, sigma3, sigma2, half_w, half_h);
     if (rc != SCAT_OK) return rc;
     const float sw[7] = {s_rots, s_poses, s_betas, s_trans, s_scale, s_cs, s_ct};
     const char* const sn[7] = {"s_rots", "s_poses", "s_betas", "s_trans", "s_scale", "s_cs", "s_ct"};
-    for (int i = 0; i < 7; ++i)
-        SCAT_REQUIRE(sw[i] >= 0.f && sw[i] < INFINITY, SCAT_E_ARG, "%s: %s %g must be finite and not negative", fn, sn[i],
-                     (double)sw[i]);
+    rc = seq_check_smooth(fn, sw, sn, 7);
+    if (rc != SCAT_OK) return rc;
     rc = fit_check_mask(fn, free_mask);
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(free_cam >= 0 && free_cam <= 7, SCAT_E_ARG, "%s: free_cam %d outside 0..7", fn, free_cam);
     SCAT_REQUIRE((int64_t)S * T <= INT32_MAX, SCAT_E_SHAPE, "%s: %d sequences of %d frames: more than %d frames", fn, S, T, INT32_MAX);
-    const int64_t need = scat_mano_fit_seq_kp_ws(S, T);
-    SCAT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "%s: the workspace must be a 16-byte-aligned pointer", fn);
-    SCAT_REQUIRE(ws_bytes >= need, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
-                 (long long)need);
+    rc = seq_check_ws(fn, ws, ws_bytes, scat_mano_fit_seq_kp_ws(S, T));
+    if (rc != SCAT_OK) return rc;
     if (init) {
         seq_kp_launch_start(a, S, (hipStream_t)stream);
         SCAT_LAUNCH_CHECK(fn);

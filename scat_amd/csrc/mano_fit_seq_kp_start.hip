@@ -22,7 +22,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_kp_start_kernel(SeqKpA
     const int64_t s = blockIdx.x / T;
     const bool has3 = a.targets3 != nullptr, has2 = a.targets2 != nullptr;
     const int64_t fr = s * T + t;
-    float* const q = a.ws + s * ((int64_t)T * kQFrame) + (int64_t)T * (kQL + kQM) + t * kKU;
+    float* const q = seq_ws_start<kKU>(a.ws, s, T, t);
     jac_load_model(m, a.m);
     if (tid < kFJoints) {
         const int v = a.joint_map[tid];

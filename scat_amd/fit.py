@@ -60,12 +60,9 @@ SEQ_MAX_T = 256                # SCAT_FIT_SEQ_MAX_T
 SMOOTH_KEYS = ("rots", "poses", "betas", "trans", "scale")      # s_rots .. s_scale, in the entry point's order
 # s_rots .. s_ct of scat_mano_fit_seq_kp, in the entry point's order: the five, then the camera's scale and its offsets
 SMOOTH_KP_KEYS = SMOOTH_KEYS + ("cam_scale", "cam_trans")
-# bound on first use by lib().bind, beside _lib.py's tables: the MANO fit to a full mesh
-FIT_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_verts.h")
-# likewise: the MANO fit to a point cloud
-FIT_POINTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_points.h")
-# likewise: the MANO fit to a track of keypoints
-FIT_SEQ_KP_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_seq_kp.h")
+# bound on first use by lib().bind, beside _lib.py's tables: the MANO fits to a full mesh, a point cloud, a track of keypoints
+FIT_VERTS_HEADER, FIT_POINTS_HEADER, FIT_SEQ_KP_HEADER = (os.path.join(HERE, "..", "include", f"scat_mano_fit_{n}.h")
+                                                          for n in ("verts", "points", "seq_kp"))
 POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
 POINTS_MAX_ROUNDS = 64         # SCAT_FIT_POINTS_MAX_ROUNDS
 POINTS_MAX_STEPS = 256         # SCAT_FIT_POINTS_MAX_STEPS: rounds * iters
@@ -183,6 +180,12 @@ def _weights(what, weights, shape):
 def _results(n, device):
     """cost [n] and accepted [n] int32 for a kernel to write"""
     return torch.empty((n,), dtype=torch.float32, device=device), torch.empty((n,), dtype=torch.int32, device=device)
+
+
+def _workspace(query, sizes, device, least=16):
+    """(ws, nbytes): a workspace of the size query(*sizes) gives (0 for sizes the launch refuses), never empty"""
+    nbytes = int(query(*sizes))
+    return torch.empty((max(nbytes, least),), dtype=torch.uint8, device=device), nbytes
 
 
 def _model_inputs(what, model, rots, poses, betas):
@@ -316,8 +319,7 @@ def mano_fit_points(model, points, weights, p, rounds, iters, max_dist, lambda0,
     idx = torch.empty((B, N), dtype=torch.int32, device=dev)
     dist = torch.empty((B, N), dtype=torch.float32, device=dev)
     ns = lib().bind(FIT_POINTS_HEADER)
-    nbytes = int(ns.scat_mano_fit_points_ws(B, N, model.V))
-    ws = torch.empty((max(nbytes, 32 * B, 16),), dtype=torch.uint8, device=dev)
+    ws, nbytes = _workspace(ns.scat_mano_fit_points_ws, (B, N, model.V), dev, max(32 * B, 16))
     ns.scat_mano_fit_points(*_model_args(model), _p(points), _p(weights), _p(p), _p(cost), _p(accepted), _p(idx), _p(dist), _p(ws),
                             nbytes, B, N, model.V, model.parents_packed, int(rounds), int(iters), float(max_dist), float(lambda0),
                             float(w_pose), float(w_beta), int(free), _stream())
@@ -346,8 +348,7 @@ def mano_fit_seq(model, targets, weights, joint_map, p, iters, init, lambda0, w_
     S, T = int(targets.shape[0]), int(targets.shape[1])
     cost, accepted = _results(S, targets.device)
     L = lib()
-    nbytes = int(L.scat_mano_fit_seq_ws(S, T))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=targets.device)
+    ws, nbytes = _workspace(L.scat_mano_fit_seq_ws, (S, T), targets.device)
     L.scat_mano_fit_seq(*_model_args(model), _p(targets), _p(weights), _p(joint_map), _p(p), _p(cost), _p(accepted), _p(ws), nbytes, S,
                         T, model.V, model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose),
                         float(w_beta), float(s_rots), float(s_poses), float(s_betas), float(s_trans), float(s_scale), int(free),
@@ -365,8 +366,7 @@ def mano_fit_seq_kp(model, targets3, weights3, targets2, weights2, joint_map, po
     S, T = int(p.shape[0]), int(p.shape[1])
     cost, accepted = _results(S, p.device)
     ns = lib().bind(FIT_SEQ_KP_HEADER)
-    nbytes = int(ns.scat_mano_fit_seq_kp_ws(S, T))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=p.device)
+    ws, nbytes = _workspace(ns.scat_mano_fit_seq_kp_ws, (S, T), p.device)
     ns.scat_mano_fit_seq_kp(*_model_args(model), _p(targets3), _p(weights3), _p(targets2), _p(weights2), _p(joint_map), _p(pose_lo),
                             _p(pose_hi), _p(p), _p(cost), _p(accepted), _p(ws), nbytes, S, T, model.V, model.parents_packed,
                             *model.tips, int(iters), int(init), float(lambda0), float(w_pose), float(w_beta), float(w_limit),
@@ -566,19 +566,30 @@ class ManoFitter:
         joints3d is None (they are a gauge of the camera then).  free_cam: bits 0, 1, 2 free cs, ctx, cty; without
         joints2d the camera has no rows and stays frozen.  A sample with a target or weight that is not finite, or a
         negative weight, is not fitted: cost +inf, accepted 0, p its start."""
-        what = "ManoFitter.fit_keypoints"
+        p, args, frees = self._keypoint_args("ManoFitter.fit_keypoints", "B", (KeypointFitResult, PointFitResult), joints3d,
+                                             joints2d, w3, w2, size, sigma3, sigma2, limits, w_limit, init, free, free_cam, iters)
+        cost, accepted = mano_fit_kp(*args, *frees)
+        return KeypointFitResult(*_groups(p), p[:, 62:65], cost, accepted, p)
+
+    def _keypoint_args(self, what, lead, result_types, joints3d, joints2d, w3, w2, size, sigma3, sigma2, limits, w_limit, init,
+                       free, free_cam, iters):
+        """The checks that fit_keypoints (lead "B": [B,21,.]) and fit_keypoints_sequence (lead "S,T": [S,T,21,.], T <= 256)
+        share -> (p, the arguments of mano_fit_kp / mano_fit_seq_kp from the model up to half_h, (free, free_cam))"""
         if joints3d is None and joints2d is None:
             raise ScatError(f"{what} needs joints3d, joints2d or both")
-        given = [t for t in (joints3d, joints2d, w3, w2) if t is not None]
-        _need_gpu(what, *given)
+        _need_gpu(what, *(t for t in (joints3d, joints2d, w3, w2) if t is not None))
         ref = joints3d if joints3d is not None else joints2d
         _check_model(what, self.model, ref)
-        B = ref.shape[0]
-        for name, t, shape in (("joints3d", joints3d, (B, 21, 3)), ("joints2d", joints2d, (B, 21, 2)), ("w3", w3, (B, 21)),
-                               ("w2", w2, (B, 21))):
-            if t is not None and (B == 0 or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != ref.device):
-                raise ScatError(f"{what} needs fp32 {name} {list(shape)} with B >= 1 on {ref.device}, got {t.dtype} "
-                                f"{tuple(t.shape)} on {t.device}")
+        n = 1 + lead.count(",")
+        if ref.dim() != n + 2 or 0 in ref.shape[:n] or (n == 2 and ref.shape[1] > SEQ_MAX_T):
+            raise ScatError(f"{what} needs fp32 joints3d [{lead},21,3] and / or joints2d [{lead},21,2] with "
+                            f"{'B >= 1' if n == 1 else f'S >= 1 and T in 1..{SEQ_MAX_T}'}, got {tuple(ref.shape)}")
+        dims = tuple(int(d) for d in ref.shape[:n])
+        for name, t, shape in (("joints3d", joints3d, (*dims, 21, 3)), ("joints2d", joints2d, (*dims, 21, 2)),
+                               ("w3", w3, (*dims, 21)), ("w2", w2, (*dims, 21))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != ref.device):
+                raise ScatError(f"{what} needs fp32 {name} {list(shape)} on {ref.device}, got {t.dtype} {tuple(t.shape)} on "
+                                f"{t.device}")
         if (w3 is not None and joints3d is None) or (w2 is not None and joints2d is None):
             raise ScatError(f"{what}: weights given without their joints")
         lo = hi = None
@@ -589,7 +600,7 @@ class ManoFitter:
         H, W = (float(v) for v in size)
         if not (H > 0 and W > 0):
             raise ScatError(f"{what}: size {size} must be positive")
-        p = _start(what, init, (KeypointFitResult, PointFitResult), (B, KP_UNKNOWNS), ref.device)
+        p = _start(what, init, result_types, (*dims, KP_UNKNOWNS), ref.device)
         iters = self.iters if iters is None else int(iters)
         if free is None:
             free = ALL_FREE if joints3d is not None else free_mask(trans=False, log_scale=False)
@@ -597,10 +608,9 @@ class ManoFitter:
         if min(float(sigma3), float(sigma2), float(w_limit)) < 0:
             raise ScatError(f"{what}: sigma3, sigma2 and w_limit must not be negative")
         c = lambda t: None if t is None else t.contiguous()
-        cost, accepted = mano_fit_kp(self.model, c(joints3d), c(w3), c(joints2d), c(w2), self._map_on(ref.device), lo, hi, p, iters,
-                                     0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma3, sigma2,
-                                     0.5 * W, 0.5 * H, free, int(free_cam) if joints2d is not None else 0)
-        return KeypointFitResult(*_groups(p), p[:, 62:65], cost, accepted, p)
+        return p, (self.model, c(joints3d), c(w3), c(joints2d), c(w2), self._map_on(ref.device), lo, hi, p, iters,
+                   0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma3, sigma2, 0.5 * W,
+                   0.5 * H), (free, int(free_cam) if joints2d is not None else 0)
 
     def fit_keypoints_sequence(self, joints3d=None, joints2d=None, w3=None, w2=None, size=(224, 224), sigma3=0.0, sigma2=0.0,
                                limits=None, w_limit=0.0, smooth=None, init=None, free=None, free_cam=7, iters=None):
@@ -626,42 +636,9 @@ class ManoFitter:
         fitted: cost +inf, accepted 0, p its start."""
         what = "ManoFitter.fit_keypoints_sequence"
         sm = _smooth(what, smooth, SMOOTH_KP_KEYS)
-        if joints3d is None and joints2d is None:
-            raise ScatError(f"{what} needs joints3d, joints2d or both")
-        given = [t for t in (joints3d, joints2d, w3, w2) if t is not None]
-        _need_gpu(what, *given)
-        ref = joints3d if joints3d is not None else joints2d
-        _check_model(what, self.model, ref)
-        if ref.dim() != 4 or ref.shape[0] == 0 or not 1 <= ref.shape[1] <= SEQ_MAX_T:
-            raise ScatError(f"{what} needs fp32 joints3d [S,T,21,3] and / or joints2d [S,T,21,2] with S >= 1 and T in "
-                            f"1..{SEQ_MAX_T}, got {tuple(ref.shape)}")
-        S, T = int(ref.shape[0]), int(ref.shape[1])
-        for name, t, shape in (("joints3d", joints3d, (S, T, 21, 3)), ("joints2d", joints2d, (S, T, 21, 2)), ("w3", w3, (S, T, 21)),
-                               ("w2", w2, (S, T, 21))):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != ref.device):
-                raise ScatError(f"{what} needs fp32 {name} {list(shape)} on {ref.device}, got {t.dtype} {tuple(t.shape)} on "
-                                f"{t.device}")
-        if (w3 is not None and joints3d is None) or (w2 is not None and joints2d is None):
-            raise ScatError(f"{what}: weights given without their joints")
-        lo = hi = None
-        if limits is not None:
-            lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(ref.device).contiguous() for t in limits)
-            if tuple(lo.shape) != (POSE,) or tuple(hi.shape) != (POSE,):
-                raise ScatError(f"{what} needs limits (lo[45], hi[45]), got {tuple(lo.shape)}, {tuple(hi.shape)}")
-        H, W = (float(v) for v in size)
-        if not (H > 0 and W > 0):
-            raise ScatError(f"{what}: size {size} must be positive")
-        p = _start(what, init, KeypointSequenceFitResult, (S, T, KP_UNKNOWNS), ref.device)
-        iters = self.iters if iters is None else int(iters)
-        if free is None:
-            free = ALL_FREE if joints3d is not None else free_mask(trans=False, log_scale=False)
-        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE and 0 <= int(free_cam) <= 7, ", or free_cam is outside 0..7")
-        if min(float(sigma3), float(sigma2), float(w_limit)) < 0:
-            raise ScatError(f"{what}: sigma3, sigma2 and w_limit must not be negative")
-        c = lambda t: None if t is None else t.contiguous()
-        cost, accepted = mano_fit_seq_kp(self.model, c(joints3d), c(w3), c(joints2d), c(w2), self._map_on(ref.device), lo, hi, p, iters,
-                                         0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma3,
-                                         sigma2, 0.5 * W, 0.5 * H, sm, free, int(free_cam) if joints2d is not None else 0)
+        p, args, frees = self._keypoint_args(what, "S,T", KeypointSequenceFitResult, joints3d, joints2d, w3, w2, size, sigma3,
+                                             sigma2, limits, w_limit, init, free, free_cam, iters)
+        cost, accepted = mano_fit_seq_kp(*args, sm, *frees)
         return KeypointSequenceFitResult(*_groups(p), p[..., 62:65], cost, accepted, p)
 
     def project(self, result, size=(224, 224)):

@@ -101,6 +101,19 @@ def test_workspace_query(built):
         assert int(q(S, T)) == 0, (S, T)
 
 
+def test_both_track_queries_share_one_layout(built):
+    """scat_mano_fit_seq_ws and scat_mano_fit_seq_kp_ws are one piece of arithmetic at 62 and at 65 unknowns (L_t with
+    y_t, M_t^T, two copies of the unknowns, fp32): 31,496 and 34,580 bytes per frame, 0 outside 1..256 frames"""
+    from scat_amd._lib import lib
+    from scat_amd.fit import FIT_SEQ_KP_HEADER
+
+    L = lib()
+    for q, per_frame in ((L.scat_mano_fit_seq_ws, 31496), (L.bind(FIT_SEQ_KP_HEADER).scat_mano_fit_seq_kp_ws, 34580)):
+        for S, T in ((1, 1), (2, 5), (1, 256)):
+            assert int(q(S, T)) == S * T * per_frame, (S, T)
+        assert int(q(1, 0)) == 0 and int(q(1, 257)) == 0
+
+
 GOOD = dict(S=2, T=5, V=778, parents=PARENTS, tips=[320, 443, 671, 554, 744], iters=20, init=1, lambda0=1e-3, w_pose=1e-6,
             w_beta=1e-6, w_limit=1e-2, sigma3=0.01, sigma2=10.0, half=[112.0, 112.0], s=[1e-3, 1e-4, 1e-2, 1e-1, 1e-1, 1e-3, 1e-1],
             free=(1 << 62) - 1, free_cam=7, ws=4096, ws_bytes=None)

@@ -5,8 +5,9 @@ compare against (SCAT_LIBPATH) and once with this tree's, each in its own proces
 (profiles/fit_family_refactor.txt is such a pair).
 
 The smallest shapes: V = 37, and 778 once per entry point; 6 hands for the joints, keypoint and mesh fits, 2 sequences of 5
-frames, a cloud of (3, 257, 37).  5 iterations; the closed-form start and the caller's; one run with a frozen group and one
-with some zero weights."""
+frames (joints and keypoints; at V = 37 also of 1 and of 2 frames, the block-tridiagonal walk's smallest), a cloud of
+(3, 257, 37).  5 iterations; the closed-form start and the caller's; one run with a frozen group and one with some zero
+weights."""
 import hashlib
 import os
 import sys
@@ -25,6 +26,7 @@ def main():
     import _fit_kp_cases as KC
     import _fit_points_cases as PC
     import _fit_seq_cases as SC
+    import _fit_seq_kp_cases as QC
     import _fit_verts_cases as VC
     from _fit_cases import JOINT_MAP, host_model
     from scat_amd import synth
@@ -84,6 +86,26 @@ def main():
         show(f"v{V}.seq.init", fitter.fit_sequence(X, smooth=SC.SMOOTH, init=near_s))
         show(f"v{V}.seq.frozen", fitter.fit_sequence(X, smooth=SC.SMOOTH, init=near_s, free=frozen))
         show(f"v{V}.seq.weights", fitter.fit_sequence(X, weights=ws, smooth=SC.SMOOTH))
+
+        _, Q3, Q2 = QC.truth(25, 2, 5, V)                        # the same tracks under a camera per sequence
+        Q3, Q2 = Q3.to(dev), Q2.to(dev)
+        near_q = QC.near_start(25, 2, 5, V).float().to(dev)
+        q2 = torch.full((2, 5, 21), QC.W2, device=dev)
+        wide = torch.full((45,), QC.WIDE_BOX)                    # active on a few angles at near_q
+        both = dict(joints3d=Q3, joints2d=Q2, w2=q2)
+        seqkp = fitter.fit_keypoints_sequence
+        show(f"v{V}.seqkp.both", seqkp(**both, smooth=QC.SMOOTH))
+        show(f"v{V}.seqkp.2d", seqkp(joints2d=Q2, smooth=QC.SMOOTH))
+        show(f"v{V}.seqkp.init", seqkp(**both, smooth=QC.SMOOTH, init=near_q, sigma3=0.01, sigma2=10.0))
+        show(f"v{V}.seqkp.limits", seqkp(**both, smooth=QC.SMOOTH, init=near_q, limits=(-wide, wide), w_limit=QC.W_LIMIT))
+        show(f"v{V}.seqkp.frozen", seqkp(**both, smooth=QC.SMOOTH, init=near_q, free=frozen, free_cam=0))
+        show(f"v{V}.seqkp.weights", seqkp(joints3d=Q3, joints2d=Q2, w3=ws, w2=q2 * ws, smooth=QC.SMOOTH))
+        show(f"v{V}.seqkp.decoupled", seqkp(**both))
+        if V == 37:      # the walk's smallest shapes: T = 1 eliminates nothing, T = 2 has one M_t and no middle frame
+            for T in (1, 2):
+                show(f"v{V}.seq.t{T}", fitter.fit_sequence(SC.track(25, 2, T, V)[1].to(dev), smooth=SC.SMOOTH))
+                _, R3, R2 = QC.truth(25, 2, T, V)
+                show(f"v{V}.seqkp.t{T}", seqkp(joints3d=R3.to(dev), joints2d=R2.to(dev), w2=q2[:, :T].contiguous(), smooth=QC.SMOOTH))
 
         show(f"v{V}.verts_jac", mano_verts_jac(fitter.model, P[:, 0:3], P[:, 3:48], P[:, 48:58]))
         show(f"v{V}.verts", fitter.fit_vertices(Tv))
