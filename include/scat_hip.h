@@ -59,6 +59,28 @@ int scat_conv2d_dgrad_s2(const float* dy, const float* w, float* dx, int B, int 
  *      <= 2^-25 of the product, below one fp32 rounding.  Default; SCAT_MATH=f32 selects 0 at load time. */
 int scat_get_math_mode(void);
 int scat_set_math_mode(int mode);
+/* Epilogue request of ONE call: the four entry points that take `ScatEpilogue* epi` (nullable, HOST memory, read and
+ * written before the call returns, not retained) can leave per-channel partial sums in `part` beside their result, so
+ * that the BatchNorm pass that would read the result back is not needed.  Which form applies follows from the call:
+ *   forward statistics — a non-accumulating call without bias: per channel (= output row) and column group the sum and
+ *     the sum of squares of the output (fp32 over <= 128 pixels), about shift[c] when `shift` is given; see
+ *     scat_bn_train_stats_partials[_shifted] below.  Reads part, part_bytes, shift.
+ *   BatchNorm backward — an accumulating scat_conv1x1_s1 data gradient without bias, x, mask and mean all non-null; see
+ *     scat_bn_bwd_pre_partials below.  Reads part, part_bytes, x, mask, mean.
+ * A call given a non-null epi always sets epi->groups: the column groups written ([rows][groups][2] floats), or 0 when
+ * this call did not do it — refused, a kernel that cannot (the fp32 engine, the 256-row pointwise tiles, a bias), or
+ * rows * groups * 8 > part_bytes; `part` is then untouched and the caller takes the separate pass.
+ * part_bytes >= rows * (ceil(B*OH*OW / 32) + 4) * 8 always suffices. */
+typedef struct ScatEpilogue {
+    float* part;            /* in: [rows][groups][2] floats, device memory */
+    int64_t part_bytes;     /* in */
+    int groups;             /* OUT: column groups written; 0 = this launch did not do it, use the separate pass */
+    const float* shift;     /* in, forward statistics only, optional: per-channel reference [rows] */
+    const float* x;         /* in, BatchNorm-backward form only: the raw input of that BatchNorm, shaped like dst, */
+    const uint8_t* mask;    /*   the sign bits of the block output (scat_bn_apply's mask_out), */
+    const float* mean;      /*   that BatchNorm's batch mean [rows] */
+} ScatEpilogue;
+int64_t scat_epilogue_bytes(void);   /* sizeof(ScatEpilogue), for bindings */
 /* 3x3 / stride 1 / pad 1 with an LDS-resident halo (every input element is fetched once per tile instead of
  * once per tap): transposed = 0 -> dst[B,Cout,H,W] = conv(relu(src*scale+shift), w), src[B,Cin,H,W];
  * transposed = 1 -> dst[B,Cin,H,W] (+)= data gradient from src = dy[B,Cout,H,W].  w is the forward weight
@@ -67,14 +89,14 @@ int scat_set_math_mode(int mode);
 int64_t scat_conv3x3_s1_ws(int Cout, int Cin);
 int scat_conv3x3_s1(const float* src, const float* w, float* dst, int B, int Cin, int H, int W, int Cout,
                     int transposed, const float* in_scale, const float* in_shift, int in_relu, int accumulate,
-                    void* ws, int64_t ws_bytes, int w_ready, void* stream);
+                    void* ws, int64_t ws_bytes, int w_ready, ScatEpilogue* epi, void* stream);
 /* Forward conv (1x1 / 3x3, stride 1 or 2) on the split-operand taps kernel: contraction ordered (tap, channel),
  * weights re-laid and split per call into ws (scat_conv2d_fwd_split_ws bytes, 16-B aligned).  Needs
  * scat_get_math_mode() == 1 and Cin % 16 == 0.  The library's path for the stride-2 convolutions (models/resnet.py:68,131-135). */
 int64_t scat_conv2d_fwd_split_ws(int Cout, int Cin, int KH, int KW);
 int scat_conv2d_fwd_split(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int H, int W,
                           int Cout, int KH, int KW, int stride, int pad, const float* in_scale, const float* in_shift,
-                          int in_relu, void* ws, int64_t ws_bytes, int w_ready, void* stream);
+                          int in_relu, void* ws, int64_t ws_bytes, int w_ready, ScatEpilogue* epi, void* stream);
 /* One transformer layer's qkv projection + softmax attention in one launch (models/vision_transformer.py:61-76):
  * qkv[B*n,3*heads*64] = h[B*n,dim] . wqkv^T; attn[B,heads,n,n] = softmax(scale q k^T); ao[B*n,heads*64] = attn . v
  * ('b n (h d)').  One workgroup per (block of 128/n images, head): the block's projection stays in LDS for its
@@ -88,7 +110,7 @@ int scat_vit_qkv_attn_fwd(const float* h, const float* wqkv, float* qkv, float* 
  * y[B,Cout,OH,OW]; ws: scat_conv7x7_s2_fwd_split_ws(Cout) bytes, 16-B aligned.  Needs scat_get_math_mode() == 1. */
 int64_t scat_conv7x7_s2_fwd_split_ws(int Cout);
 int scat_conv7x7_s2_fwd_split(const float* x, const float* w, float* y, int B, int H, int W, int Cout, void* ws,
-                              int64_t ws_bytes, void* stream);
+                              int64_t ws_bytes, ScatEpilogue* epi, void* stream);
 /* Weight gradient of that stem convolution: dw[64,3,7,7] from dy[B,64,OH,OW] and x[B,3,H,W]; one workgroup walks whole
  * output rows with the 7 x 3 input rows they touch in LDS, both MFMA operands split in registers, deterministic split
  * over output rows + fixed-order reduce.  Cout = 64, OW % 16 == 0, OW <= 112.  ws: ..._ws(B, H, W) bytes, 16-B aligned
@@ -105,7 +127,7 @@ int scat_conv7x7_s2_wgrad_split(const float* dy, const float* x, float* dw, int 
 int64_t scat_conv1x1_s1_ws(int M, int C);
 int scat_conv1x1_s1(const float* src, const float* w, float* dst, int B, int C, int HW, int M, int transposed,
                     const float* bias, const float* in_scale, const float* in_shift, int in_relu, int accumulate,
-                    void* ws, int64_t ws_bytes, int w_ready, void* stream);
+                    void* ws, int64_t ws_bytes, int w_ready, ScatEpilogue* epi, void* stream);
 /* ---- activations as pre-split bf16 planes ("P8" layout) ----
  * The split-operand kernels form an fp32 product from the three bf16 terms hi + mid + lo of each operand; an activation
  * tensor can be handed over already split:  planes[p][n][c / 8][pixel][c % 8]  (bf16; p = hi, mid, lo; C % 8 == 0;
@@ -201,18 +223,12 @@ int scat_bn_train_stats(const float* x, int B, int C, int HW, const float* gamma
                         float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
                         float* save_invstd, float* scale, float* shift, void* ws, int64_t ws_bytes, void* stream);
 /* The same statistics without reading the convolution output back (the reference's nn.BatchNorm2d after nn.Conv2d,
- * models/resnet.py:65-73): scat_epilogue_stats_arm(buf, bytes) before a forward convolution call makes its kernel, if it
- * is one of the split-operand kernels, leave per-tile row sums (sum, sum of squares; fp32 over <= 128 pixels) in buf
- * ([C][groups][2] floats; bytes >= C * (ceil(B*OH*OW / 32) + 4) * 8 always suffices); scat_epilogue_stats_groups() right after
- * the call returns `groups` (0: that kernel does not write them — use scat_bn_train_stats) and disarms.  The state is per
- * host thread.  scat_bn_train_stats_partials sums the partials in fp64 in a fixed order and finishes as above. */
-int scat_epilogue_stats_arm(float* buf, int64_t bytes);
-int scat_epilogue_stats_groups(void);
-/* The same with a per-channel reference c[C] (device pointer, e.g. the previous step's batch mean): the kernel leaves the
- * sums of (x - c) and (x - c)^2 instead — fp32 sums of x^2 over 32..128 pixels cancel catastrophically in
- * E[x^2] - mean^2 when |mean| >> sigma — and scat_bn_train_stats_partials_shifted(partials, groups, c, ...) finishes
- * mean = c + S1/N, var = S2/N - (S1/N)^2.  c must stay unchanged until that call has run. */
-int scat_epilogue_stats_arm_shift(float* buf, int64_t bytes, const float* shift);
+ * models/resnet.py:65-73): a forward convolution given a ScatEpilogue (above) leaves per-tile row sums in its `part` and
+ * reports `groups`; scat_bn_train_stats_partials sums the partials in fp64 in a fixed order and finishes as above.
+ * With ScatEpilogue.shift = c[C] (device pointer, e.g. the previous step's batch mean) the kernel leaves the sums of
+ * (x - c) and (x - c)^2 instead — fp32 sums of x^2 over 32..128 pixels cancel catastrophically in E[x^2] - mean^2 when
+ * |mean| >> sigma — and scat_bn_train_stats_partials_shifted(partials, groups, c, ...) finishes mean = c + S1/N,
+ * var = S2/N - (S1/N)^2.  c must stay unchanged until that call has run. */
 int scat_bn_train_stats_partials(const float* partials, int groups, int B, int C, int HW, const float* gamma,
                                  const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                                  float* save_mean, float* save_invstd, float* scale, float* shift, void* stream);
@@ -256,16 +272,11 @@ int scat_bn_bwd_pre(float* dy_g, const float* dy_add, const float* x, const floa
                     float* dgamma, float* dbeta, float* coef3, int B, int C, int HW, void* ws, int64_t ws_bytes,
                     void* stream);
 /* The reduction of that first half inside the kernel that COMPLETES the gradient (models/resnet.py:93-96: the gradient of a
- * block output is the next block's conv1 data gradient accumulated onto the shortcut's gradient): armed before an
- * accumulating scat_conv1x1_s1 call, the kernel — if it is one that can (128-row tiles on split products; others ignore it)
- * — masks the completed gradient with the output's sign bits `mask` (scat_bn_apply's mask_out), stores the MASKED gradient
- * and leaves per channel and column group the sums of g and g * (x - mean[c]) in `part` ([C][groups][2] floats; bytes >=
- * C * (ceil(B*HW / 32) + 4) * 8 always suffices).  x: the raw output of the convolution in front of that BatchNorm, n floats
- * (= the size of the gradient tensor).  scat_epilogue_bnb_groups() right after the call returns the number of groups written
- * (0: not done, use scat_bn_bwd_pre) and disarms; scat_bn_bwd_pre_partials finishes coef3 / dgamma / dbeta from them.  Same
- * host-thread, one-shot protocol as scat_epilogue_stats_arm. */
-int scat_epilogue_bnb_arm(const float* x, const uint8_t* mask, const float* mean, int64_t n, float* part, int64_t part_bytes);
-int scat_epilogue_bnb_groups(void);
+ * block output is the next block's conv1 data gradient accumulated onto the shortcut's gradient): an accumulating
+ * scat_conv1x1_s1 call given a ScatEpilogue with x, mask and mean (above) — if its kernel is one that can (128-row tiles on
+ * split products; others report 0 groups) — masks the completed gradient with the output's sign bits, stores the MASKED
+ * gradient and leaves per channel and column group the sums of g and g * (x - mean[c]) in `part`.  0 groups: not done, use
+ * scat_bn_bwd_pre; else scat_bn_bwd_pre_partials finishes coef3 / dgamma / dbeta from them. */
 int scat_bn_bwd_pre_partials(const float* partials, int groups, int B, int C, int HW, const float* save_mean,
                              const float* save_invstd, const float* gamma, float* dgamma, float* dbeta, float* coef3,
                              void* stream);

@@ -41,6 +41,13 @@ _CT = {
 }
 
 
+class HostInOut(ctypes.c_void_p):
+    """an argument like ``ScatEpilogue* epi``: a non-const pointer to one of the header's own structs.  It is HOST memory
+    that the entry point reads and writes before its first check, so it is null or the address of a real struct, never a
+    made-up integer as a device pointer may be in a call that is to stop in the host code.  Its own type, so that code
+    which fabricates every ``c_void_p`` argument leaves this one null; it takes what ``c_void_p`` takes."""
+
+
 def parse_header(path: str = HEADER):
     """-> {name: (restype, [(ctype, argname)])} for every prototype in the header."""
     src = open(path).read()
@@ -54,7 +61,7 @@ def parse_header(path: str = HEADER):
             for a in args.split(","):
                 a = a.strip()
                 if "*" in a:
-                    at.append((ctypes.c_void_p, a.split("*")[-1].strip()))
+                    at.append((HostInOut if re.match(r"Scat\w+\s*\*", a) else ctypes.c_void_p, a.split("*")[-1].strip()))
                 else:
                     ty, an = a.rsplit(" ", 1)
                     at.append((_CT[ty.replace("const ", "").strip()], an))
@@ -97,8 +104,7 @@ class _Lib:
         fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = rt
         fn.argtypes = [t for t, _ in at]
-        if rt is ctypes.c_int and name not in ("scat_version", "scat_get_math_mode", "scat_epilogue_stats_groups",
-                                                  "scat_epilogue_bnb_groups"):
+        if rt is ctypes.c_int and name not in ("scat_version", "scat_get_math_mode"):
             return self._checked(fn, name)
         return fn
 

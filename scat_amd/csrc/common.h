@@ -21,15 +21,14 @@ constexpr bool kDiag = false;
 void set_error(const char* fmt, ...);
 void set_kernel_label(const char* fmt, ...);   // which engine instantiation the last call launched
 void append_kernel_label(const char* suffix);
-// scat_epilogue_stats_arm: the next contraction launched from this thread may write per-tile row sums into the armed
-// buffer.  A launcher that supports it calls this with the rows and column groups of its grid: returns the buffer (and
-// records the group count for scat_epilogue_stats_groups) when one is armed and large enough, else nullptr.
-// *shift (optional out): the per-row reference the sums are taken about (scat_epilogue_stats_arm_shift), or nullptr
-float* epi_stats_take(int rows, int groups, const float** shift = nullptr);
-// BatchNorm-backward epilogue armed by the caller for the next qualifying accumulate launch of this host thread
-// (scat_epilogue_bnb_arm): true when armed and the buffers fit (rows x groups partial pairs, a tensor of n floats)
-struct EpiBnb { const float* x; const uint8_t* mask; const float* mean; float* part; int64_t cap; int64_t n; int groups; };
-bool epi_bnb_take(int rows, int groups, int64_t n, EpiBnb* out);
+// A call's epilogue request (ScatEpilogue, scat_hip.h) travels beside OutDesc as a host-only pointer, null where the
+// caller offers none.  A launcher that can write the sums asks with the rows and column groups of its grid: true, and
+// the group count recorded in the request, when there is one and its `part` holds rows x groups pairs.
+static inline bool epi_fits(ScatEpilogue* e, int rows, int groups) {
+    if (!e || !e->part || (int64_t)rows * groups * 2 > e->part_bytes / 4) return false;
+    e->groups = groups;
+    return true;
+}
 
 // Every entry point returns through these: no exception crosses the C boundary.
 #define SCAT_REQUIRE(cond, code, ...)          \

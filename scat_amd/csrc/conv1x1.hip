@@ -903,23 +903,22 @@ static int pw_plain_mode() {
 }
 
 template <int WM, int BN, bool TF, bool DS = false, bool STEM = false>
-static void launch_pw_split(const PwDesc& d, const OutDesc& dc_in, hipStream_t st) {
+static void launch_pw_split(const PwDesc& d, const OutDesc& dc_in, hipStream_t st, ScatEpilogue* epi = nullptr) {
     constexpr int BM = 32 * WM;
     const int mt = cdiv(d.M, BM), nt = cdiv(d.npix, BN);
     constexpr size_t lds_bytes = (size_t)2 * 12 * BN * 16;
     OutDesc dc = dc_in;
     if (!dc.accumulate && !dc.bias) {                 // a forward convolution: its BatchNorm's sums ride in the epilogue
         dc.sg = nt * (4 / WM);
-        dc.stats = epi_stats_take(d.M, dc.sg, &dc.stats_shift);
+        if (epi_fits(epi, d.M, dc.sg)) { dc.stats = epi->part; dc.stats_shift = epi->shift; }
     }
     if (!dc.accumulate) dc.st_aux = store_policy(dc.n * 4);
     if constexpr (!STEM && !DS && !TF && WM == 4 && BN == 128) {
         // a data gradient that completes the gradient of a block output (C += ...): the BatchNorm backward's reduction
-        // of the block that produced it rides in the epilogue when the caller armed it (scat_epilogue_bnb_arm)
-        EpiBnb eb;
-        if (dc.accumulate && !dc.bias && dc.mode == 1 && d.ntap == 1 && d.C % 32 == 0 && pw_plain_mode() &&
-            epi_bnb_take(d.M, nt * (4 / WM), dc.n, &eb)) {
-            dc.bnb_x = eb.x; dc.bnb_mask = eb.mask; dc.bnb_mean = eb.mean; dc.bnb_part = eb.part;
+        // of the block that produced it rides in the epilogue when the caller asks for it (ScatEpilogue x / mask / mean)
+        if (dc.accumulate && !dc.bias && dc.mode == 1 && d.ntap == 1 && d.C % 32 == 0 && pw_plain_mode() && epi &&
+            epi->x && epi->mask && epi->mean && epi_fits(epi, d.M, nt * (4 / WM))) {
+            dc.bnb_x = epi->x; dc.bnb_mask = epi->mask; dc.bnb_mean = epi->mean; dc.bnb_part = epi->part;
             dc.bnb_sg = nt * (4 / WM);
             hipLaunchKernelGGL((conv1x1_split_kernel<WM, BN, TF, DS, false, true, true>), dim3(mt * nt), dim3(NT), lds_bytes,
                                st, d, dc);
@@ -945,21 +944,22 @@ static const char* pw_tile_name(int cfg) {
 }
 
 template <bool DS = false, bool STEM = false>
-static void launch_pw_split_cfg(int cfg, bool tf, const PwDesc& d, const OutDesc& dc, hipStream_t st) {
+static void launch_pw_split_cfg(int cfg, bool tf, const PwDesc& d, const OutDesc& dc, hipStream_t st,
+                                ScatEpilogue* epi = nullptr) {
     if constexpr (!DS && !STEM) {
         if (tf) {
-            if (cfg == 0) launch_pw_split<4, 128, true>(d, dc, st);
-            else if (cfg == 1) launch_pw_split<2, 128, true>(d, dc, st);
-            else launch_pw_split<2, 64, true>(d, dc, st);
+            if (cfg == 0) launch_pw_split<4, 128, true>(d, dc, st, epi);
+            else if (cfg == 1) launch_pw_split<2, 128, true>(d, dc, st, epi);
+            else launch_pw_split<2, 64, true>(d, dc, st, epi);
             return;
         }
         if (cfg == 2) {
-            launch_pw_split<2, 64, false>(d, dc, st);
+            launch_pw_split<2, 64, false>(d, dc, st, epi);
             return;
         }
     }
-    if (cfg == 0) launch_pw_split<4, 128, false, DS, STEM>(d, dc, st);
-    else launch_pw_split<2, 128, false, DS, STEM>(d, dc, st);
+    if (cfg == 0) launch_pw_split<4, 128, false, DS, STEM>(d, dc, st, epi);
+    else launch_pw_split<2, 128, false, DS, STEM>(d, dc, st, epi);
 }
 
 // Geometry of a pointwise problem (one tap, stride 1): B images of C channels x HW pixels, M output rows.
@@ -1033,7 +1033,7 @@ int64_t taps_split_ws(int M, int C, int ntap) { return (int64_t)ntap * M * ((C +
 
 void taps_split_launch(const TapsGeom& g, const float* src, const float* w, const OutDesc& dc, int B, int C, int M,
                        const float* in_scale, const float* in_shift, int in_relu, void* ws, const char* label,
-                       hipStream_t st, bool w_ready) {
+                       hipStream_t st, bool w_ready, ScatEpilogue* epi) {
     PwDesc d{};
     d.src = src; d.scale = in_scale; d.shift = in_shift; d.relu = in_scale ? in_relu : 0;
     d.C = C; d.M = M; d.HW = g.H * g.W; d.npix = B * g.OH * g.OW; d.dHW = FastDiv::make(d.HW);
@@ -1050,7 +1050,7 @@ void taps_split_launch(const TapsGeom& g, const float* src, const float* w, cons
     if ((int64_t)cdiv(M, 128) * cdiv(d.npix, 128) < 256 && (int64_t)cdiv(M, 64) * cdiv(d.npix, 64) >= 256) cfg = 2;
     if (tuning() >= 1 && tuning() <= 3) cfg = tuning() - 1;
     set_kernel_label("%s_split_%sx32%s", label, pw_tile_name(cfg), in_scale ? "_tf" : "");
-    launch_pw_split_cfg(cfg, in_scale != nullptr, d, dc, st);
+    launch_pw_split_cfg(cfg, in_scale != nullptr, d, dc, st, epi);
 }
 
 }  // namespace scat
@@ -1067,7 +1067,8 @@ extern "C" int64_t scat_conv2d_fwd_split_ws(int Cout, int Cin, int KH, int KW) {
 extern "C" int scat_conv2d_fwd_split(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int H,
                                      int W, int Cout, int KH, int KW, int stride, int pad, const float* in_scale,
                                      const float* in_shift, int in_relu, void* ws, int64_t ws_bytes, int w_ready,
-                                     void* stream) {
+                                     ScatEpilogue* epi, void* stream) {
+    if (epi) epi->groups = 0;
     int OH, OW;
     if (int e = check_geom("scat_conv2d_fwd_split", B, Cin, H, W, Cout, KH, KW, stride, pad, &OH, &OW)) return e;
     SCAT_REQUIRE(x && w && y, SCAT_E_ARG, "scat_conv2d_fwd_split: null pointer");
@@ -1085,7 +1086,7 @@ extern "C" int scat_conv2d_fwd_split(const float* x, const float* w, const float
     char label[32];
     snprintf(label, sizeof label, "conv%dx%d_s%d", KH, KW, stride);
     taps_split_launch(g, x, w, dc, B, Cin, Cout, in_scale, in_shift, in_relu, ws, label, (hipStream_t)stream,
-                      w_ready != 0);
+                      w_ready != 0, epi);
     SCAT_LAUNCH_CHECK("scat_conv2d_fwd_split");
     return SCAT_OK;
 }
@@ -1095,7 +1096,8 @@ extern "C" int64_t scat_conv7x7_s2_fwd_split_ws(int Cout) { return (int64_t)12 *
 // The ResNet stem (models/resnet.py:105: Conv2d(3, 64, 7, stride 2, padding 3, bias=False)) on split-operand products:
 // y[B,Cout,OH,OW] = conv(x[B,3,H,W], w[Cout,3,7,7]).  ws: scat_conv7x7_s2_fwd_split_ws(Cout) bytes.
 extern "C" int scat_conv7x7_s2_fwd_split(const float* x, const float* w, float* y, int B, int H, int W, int Cout,
-                                         void* ws, int64_t ws_bytes, void* stream) {
+                                         void* ws, int64_t ws_bytes, ScatEpilogue* epi, void* stream) {
+    if (epi) epi->groups = 0;
     SCAT_REQUIRE(x && w && y, SCAT_E_ARG, "scat_conv7x7_s2_fwd_split: null pointer");
     SCAT_REQUIRE(math_mode() == 1, SCAT_E_ARG, "scat_conv7x7_s2_fwd_split: needs the split-operand product mode");
     SCAT_REQUIRE(B > 0 && H > 6 && W > 6 && Cout > 0, SCAT_E_SHAPE, "scat_conv7x7_s2_fwd_split: bad dimension");
@@ -1118,7 +1120,7 @@ extern "C" int scat_conv7x7_s2_fwd_split(const float* x, const float* w, float* 
     dc.n = (int64_t)B * Cout * OH * OW;
     const int cfg = Cout > 64 ? 0 : 1;
     set_kernel_label("conv7x7_s2_split_%sx32", pw_tile_name(cfg));
-    launch_pw_split_cfg<false, true>(cfg, false, d, dc, st);
+    launch_pw_split_cfg<false, true>(cfg, false, d, dc, st, epi);
     SCAT_LAUNCH_CHECK("scat_conv7x7_s2_fwd_split");
     return SCAT_OK;
 }
@@ -1165,7 +1167,9 @@ extern "C" int64_t scat_conv1x1_s1_ws(int M, int C) { return (int64_t)M * ((C + 
 // Needs C % 16 == 0 and 16-B aligned w/src; callers fall back to scat_conv2d_fwd / scat_conv2d_dgrad otherwise.
 extern "C" int scat_conv1x1_s1(const float* src, const float* w, float* dst, int B, int C, int HW, int M,
                                int transposed, const float* bias, const float* in_scale, const float* in_shift,
-                               int in_relu, int accumulate, void* ws, int64_t ws_bytes, int w_ready, void* stream) {
+                               int in_relu, int accumulate, void* ws, int64_t ws_bytes, int w_ready, ScatEpilogue* epi,
+                               void* stream) {
+    if (epi) epi->groups = 0;
     SCAT_REQUIRE(src && w && dst, SCAT_E_ARG, "scat_conv1x1_s1: null pointer");
     SCAT_REQUIRE(!w_ready || math_mode() == 1, SCAT_E_ARG, "scat_conv1x1_s1: prepared weights exist for split products only");
     SCAT_REQUIRE(ws && ws_bytes >= scat_conv1x1_s1_ws(M, C), SCAT_E_WORKSPACE, "scat_conv1x1_s1: workspace too small");
@@ -1220,7 +1224,7 @@ extern "C" int scat_conv1x1_s1(const float* src, const float* w, float* dst, int
             return SCAT_OK;
         }
         set_kernel_label("conv1x1_split_%sx32%s", pw_tile_name(cfg), in_scale ? "_tf" : "");
-        launch_pw_split_cfg(cfg, in_scale != nullptr, d, dc, st);
+        launch_pw_split_cfg(cfg, in_scale != nullptr, d, dc, st, epi);
         SCAT_LAUNCH_CHECK("scat_conv1x1_s1");
         return SCAT_OK;
     }

@@ -431,14 +431,14 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_split_kernel(HaloDesc d, OutDes
 // (split-operand weights: wt[t][ch][plane][i][16 bf16], the shared re-layout of conv_common.h's WPrepJob with 9 taps)
 
 template <int WM, int HB_N, bool TF>
-static void launch_split(const HaloDesc& d, const OutDesc& dc_in, hipStream_t st) {
+static void launch_split(const HaloDesc& d, const OutDesc& dc_in, hipStream_t st, ScatEpilogue* epi) {
     constexpr int BM = 32 * WM;
     const int mt = cdiv(d.M, BM), nt = cdiv(d.npix, HB_N);
     const size_t lds_bytes = (size_t)2 * 6 * d.RS * 16;
     OutDesc dc = dc_in;
     if (!dc.accumulate && !dc.bias) {                 // a forward convolution: its BatchNorm's sums ride in the epilogue
         dc.sg = nt * (4 / WM);
-        dc.stats = epi_stats_take(d.M, dc.sg, &dc.stats_shift);
+        if (epi_fits(epi, d.M, dc.sg)) { dc.stats = epi->part; dc.stats_shift = epi->shift; }
     }
     if (!dc.accumulate) dc.st_aux = store_policy(dc.n * 4);
     auto kern = conv3x3_split_kernel<WM, HB_N, TF>;
@@ -467,7 +467,9 @@ extern "C" int64_t scat_conv3x3_s1_ws(int Cout, int Cin) {
 // w is always the forward weight [Cout][Cin][3][3].
 extern "C" int scat_conv3x3_s1(const float* src, const float* w, float* dst, int B, int Cin, int H, int W, int Cout,
                                int transposed, const float* in_scale, const float* in_shift, int in_relu,
-                               int accumulate, void* ws, int64_t ws_bytes, int w_ready, void* stream) {
+                               int accumulate, void* ws, int64_t ws_bytes, int w_ready, ScatEpilogue* epi,
+                               void* stream) {
+    if (epi) epi->groups = 0;
     int OH, OW;
     if (int e = check_geom("scat_conv3x3_s1", B, Cin, H, W, Cout, 3, 3, 1, 1, &OH, &OW)) return e;
     SCAT_REQUIRE(src && w && dst, SCAT_E_ARG, "scat_conv3x3_s1: null pointer");
@@ -519,20 +521,20 @@ extern "C" int scat_conv3x3_s1(const float* src, const float* w, float* dst, int
         if (Cdst <= 32 && thin32 && !(tuning() >= 1 && tuning() <= 3)) {
             d.RS = 128 + 2 * (W + 1);
             set_kernel_label("conv3x3_split_32x128x16%s%s", transposed ? "_dgrad" : "", in_scale ? "_tf" : "");
-            if (in_scale) launch_split<1, 128, true>(d, dc, st);
-            else launch_split<1, 128, false>(d, dc, st);
+            if (in_scale) launch_split<1, 128, true>(d, dc, st, epi);
+            else launch_split<1, 128, false>(d, dc, st, epi);
             SCAT_LAUNCH_CHECK("scat_conv3x3_s1");
             return SCAT_OK;
         }
         set_kernel_label("conv3x3_split_%dx%dx16%s%s", cfg == 0 ? 128 : 64, cfg == 2 ? 64 : 128, transposed ? "_dgrad" : "", in_scale ? "_tf" : "");
         if (in_scale) {
-            if (cfg == 0) launch_split<4, 128, true>(d, dc, st);
-            else if (cfg == 1) launch_split<2, 128, true>(d, dc, st);
-            else launch_split<2, 64, true>(d, dc, st);
+            if (cfg == 0) launch_split<4, 128, true>(d, dc, st, epi);
+            else if (cfg == 1) launch_split<2, 128, true>(d, dc, st, epi);
+            else launch_split<2, 64, true>(d, dc, st, epi);
         } else {
-            if (cfg == 0) launch_split<4, 128, false>(d, dc, st);
-            else if (cfg == 1) launch_split<2, 128, false>(d, dc, st);
-            else launch_split<2, 64, false>(d, dc, st);
+            if (cfg == 0) launch_split<4, 128, false>(d, dc, st, epi);
+            else if (cfg == 1) launch_split<2, 128, false>(d, dc, st, epi);
+            else launch_split<2, 64, false>(d, dc, st, epi);
         }
         SCAT_LAUNCH_CHECK("scat_conv3x3_s1");
         return SCAT_OK;

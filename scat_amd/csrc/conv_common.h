@@ -30,9 +30,10 @@ struct TapsGeom {
 };
 int64_t taps_split_ws(int M, int C, int ntap);
 // w_ready: ws already holds this call's re-laid weights (scat_wprep_run), skip the re-layout launch
+// epi: the caller's epilogue request (common.h epi_fits), null where the entry point offers none
 void taps_split_launch(const TapsGeom& g, const float* src, const float* w, const OutDesc& dc, int B, int C, int M,
                        const float* in_scale, const float* in_shift, int in_relu, void* ws, const char* label,
-                       hipStream_t st, bool w_ready = false);
+                       hipStream_t st, bool w_ready = false, ScatEpilogue* epi = nullptr);
 
 // One weight re-layout for the split-operand kernels: dst[tap][chunk][plane][i][16 bf16] = the three bf16 terms of
 // element (i, c) of tap (kh0 + ts*(t / KWt), kw0 + ts*(t % KWt)) of w[Cout][Cin][KH][KW]; (i, c) = (co, ci), or

@@ -72,11 +72,11 @@ struct OutDesc {
     int64_t n;            // floats addressable from p (+ z*sz in mode 0): buffer bounds
     float* stats;         // optional: per-row (sum, sum of squares) of every wavefront's live columns of the tile,
     int sg;               //   stats[(row * sg + group) * 2 + {0, 1}], group = tile column * WN + wn  (BatchNorm statistics
-                          //   of a convolution's output without reading it back: scat_epilogue_stats_arm)
+                          //   of a convolution's output without reading it back: ScatEpilogue)
     int st_aux;                 // cache policy of the epilogue's stores (store_tile): 0 default, 16 sc1, 2 nt
     const float* stats_shift;   // optional per-row reference c[row]: the sums are of (x - c) and (x - c)^2 — fp32 partials of
-                                // x^2 cancel catastrophically in E[x^2] - mean^2 when |mean| >> sigma (scat_epilogue_stats_arm_shift)
-    // BatchNorm-backward epilogue (store_tile<..., BNB = true>, accumulate only; scat_epilogue_bnb_arm): the tensor being
+                                // x^2 cancel catastrophically in E[x^2] - mean^2 when |mean| >> sigma (ScatEpilogue::shift)
+    // BatchNorm-backward epilogue (store_tile<..., BNB = true>, accumulate only; ScatEpilogue x / mask / mean): the tensor being
     // completed is the gradient of  relu(bn(x) + residual)  — mask it with the output's sign bits (bit e % 4 of byte
     // e / 4), store the MASKED gradient g, and leave per row (= channel) and column group the sums of g and
     // g * (x - bnb_mean[row]) in bnb_part[(row * bnb_sg + group) * 2 + {0, 1}]: the reduction pass of that BatchNorm's

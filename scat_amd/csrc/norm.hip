@@ -1211,7 +1211,7 @@ extern "C" int scat_bn_bwd_pre(float* dy_g, const float* dy_add, const float* x,
     return SCAT_OK;
 }
 
-// coef3 / dgamma / dbeta of scat_bn_bwd_pre from the partial sums a data-gradient epilogue wrote (scat_epilogue_bnb_arm):
+// coef3 / dgamma / dbeta of scat_bn_bwd_pre from the partial sums a data-gradient epilogue wrote (ScatEpilogue):
 // the masked gradient is already in place, this is only the finish
 extern "C" int scat_bn_bwd_pre_partials(const float* partials, int groups, int B, int C, int HW, const float* save_mean,
                                         const float* save_invstd, const float* gamma, float* dgamma, float* dbeta,

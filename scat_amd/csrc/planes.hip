@@ -294,15 +294,10 @@ extern "C" int scat_planes_from_f32(const float* src, void* planes, int B, int C
 }
 
 template <int WM, int BN, int NB, int DIAG = 0>
-static void launch_pw_planes(const PlDesc& d, const OutDesc& dc_in, hipStream_t st) {
+static void launch_pw_planes(const PlDesc& d, const OutDesc& dc, hipStream_t st) {
     constexpr int BM = 32 * WM;
     const int mt = cdiv(d.M, BM), nt = cdiv(d.npix, BN);
     constexpr size_t lds_bytes = (size_t)NB * 12 * BN * 16;
-    OutDesc dc = dc_in;
-    if (!dc.accumulate && !dc.bias) {                 // a forward convolution: its BatchNorm's sums ride in the epilogue
-        dc.sg = nt * (4 / WM);
-        dc.stats = epi_stats_take(d.M, dc.sg, &dc.stats_shift);
-    }
     auto kern = pw_planes_kernel<WM, BN, NB, DIAG>;
     if constexpr (lds_bytes > 64 * 1024) {
         static bool once = (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,

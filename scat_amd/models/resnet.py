@@ -237,7 +237,7 @@ def _block_backward(bc, rec, dcur, nxt=None, pre3=None):
 
     nxt: the record of the block whose OUTPUT this block's input is (the next call's ``rec``), or None.  When this block's
     shortcut is the identity, its last kernel — conv1's data gradient, accumulated onto the masked gradient — completes the
-    gradient of that block's output: armed (EPI_BNB), its epilogue applies that block's output mask and leaves the sums
+    gradient of that block's output: asked to (EPI_BNB), its epilogue applies that block's output mask and leaves the sums
     of its bn3 backward, and the next call receives them as ``pre3`` = (partials, groups) instead of running the
     reduction pass over the three tensors again."""
     blk, xin, c1, s1, c2, s2, c3, s3, cd, sd, out, omask = rec
@@ -333,16 +333,12 @@ def _block_backward(bc, rec, dcur, nxt=None, pre3=None):
         dcur = ops.conv1x1_dgrad_bnb(da1, c1, coef1, w1, tuple(xin.shape), out=dxin, accumulate=dxin is not None,
                                      wp=wp)
     else:
-        arm = (EPI_BNB and nxt is not None and dxin is not None and pending[0] is None and _fold3(bc, nxt)
+        bnb = (EPI_BNB and nxt is not None and dxin is not None and pending[0] is None and _fold3(bc, nxt)
                and nxt[10].data_ptr() == xin.data_ptr())
-        if arm:
-            part = ops.epilogue_bnb_arm(nxt[6], nxt[11], nxt[7].mean)
-        try:
-            dcur = ops.conv2d_dgrad_w(dc1, w1, tuple(xin.shape), 1, 0, out=dxin, accumulate=dxin is not None, wp=wp)
-        finally:
-            groups = ops.epilogue_bnb_groups() if arm else 0
-        if groups:
-            pre_next = (part, groups)
+        dcur = ops.conv2d_dgrad_w(dc1, w1, tuple(xin.shape), 1, 0, out=dxin, accumulate=dxin is not None, wp=wp,
+                                  bnb=(nxt[6], nxt[11], nxt[7].mean) if bnb else None)
+        if bnb:
+            pre_next = dcur.scat_bnb
     if cd is not None:
         dcur = ops.conv2d_dgrad_w(dcd, dsw, tuple(xin.shape), blk.stride, 0, out=dcur, accumulate=True, wp=wp)
     return dcur, pre_next

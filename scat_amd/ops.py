@@ -243,7 +243,7 @@ def conv2d_fwd(x, w, stride, pad, in_scale=None, in_shift=None, in_relu=False, b
                stats=False, stats_shift=None):
     """wp: the network's WeightPrep (prepared weights), or None: the call re-lays its weights itself.
     stats: a training-mode BatchNorm follows — ask the kernel to leave the per-tile channel sums of its output behind
-    (include/scat_hip.h scat_epilogue_stats_arm); ``y.scat_stats`` = (partials, groups) when it did, for
+    (include/scat_hip.h ScatEpilogue); ``y.scat_stats`` = (partials, groups) when it did, for
     ``bn_train_stats`` to finish without reading y back."""
     if not (stats and EPI_STATS and bias is None):
         return _conv2d_fwd(x, w, stride, pad, in_scale, in_shift, in_relu, bias, out, wp)
@@ -257,26 +257,20 @@ def conv2d_fwd(x, w, stride, pad, in_scale=None, in_shift=None, in_relu=False, b
     if stats_shift is not None and not (stats_shift.device == x.device and stats_shift.dtype == torch.float32
                                         and stats_shift.is_contiguous() and stats_shift.numel() == Cout):
         stats_shift = None
-    if stats_shift is not None:
-        lib().scat_epilogue_stats_arm_shift(_p(part), nbytes, _p(stats_shift))
-    else:
-        lib().scat_epilogue_stats_arm(_p(part), nbytes)
-    try:
-        y = _conv2d_fwd(x, w, stride, pad, in_scale, in_shift, in_relu, bias, out, wp)
-    finally:
-        groups = lib().scat_epilogue_stats_groups()
-    # the partials live in a recycled workspace: they are only good until the next armed convolution on this stream.
-    # Protocol (same host thread): arm -> convolution -> groups() -> [bn_train_stats takes them]; any other armed
-    # convolution in between bumps the generation and bn_train_stats falls back to the pass over y.
+    epi = _Epilogue(_p(part), nbytes, 0, _p(stats_shift))
+    y = _conv2d_fwd(x, w, stride, pad, in_scale, in_shift, in_relu, bias, out, wp, epi)
+    # the partials live in a recycled workspace: they are only good until the next convolution that asks for them on
+    # this stream: it bumps the generation and bn_train_stats falls back to the pass over y.
     _EPI_GEN[0] += 1
-    y.scat_stats = (part, groups, _EPI_GEN[0], stats_shift) if groups > 0 else None
+    y.scat_stats = (part, epi.groups, _EPI_GEN[0], stats_shift) if epi.groups > 0 else None
     return y
 
 
 _EPI_GEN = [0]
 
 
-def _conv2d_fwd(x, w, stride, pad, in_scale=None, in_shift=None, in_relu=False, bias=None, out=None, wp=None):
+def _conv2d_fwd(x, w, stride, pad, in_scale=None, in_shift=None, in_relu=False, bias=None, out=None, wp=None, epi=None):
+    epi = 0 if epi is None else ctypes.addressof(epi)      # (scat_conv2d_fwd takes none)
     _chk(x, w, in_scale, in_shift, bias)
     B, Cin, H, W = x.shape
     Cout, _, KH, KW = w.shape
@@ -285,7 +279,7 @@ def _conv2d_fwd(x, w, stride, pad, in_scale=None, in_shift=None, in_relu=False, 
     if _pw_ok(KH, KW, stride, pad, Cin, x, w, in_scale, in_shift):
         ws, rdy = _wp_ws(wp, w, WPREP_CONV1X1_FWD, Cout, Cin, 1, 1, 0, lib().scat_conv1x1_s1_ws(Cout, Cin), x.device)
         _prof(2.0 * B * OH * OW * Cout * Cin, lib().scat_conv1x1_s1, _p(x), _p(w), _p(y), B, Cin, H * W, Cout, 0,
-              _p(bias), _p(in_scale), _p(in_shift), int(in_relu), 0, _p(ws), ws.numel(), rdy, _stream())
+              _p(bias), _p(in_scale), _p(in_shift), int(in_relu), 0, _p(ws), ws.numel(), rdy, epi, _stream())
         return y
     if (stride == 2 and KH in (1, 3) and KW == KH and Cin % 16 == 0 and lib().scat_get_math_mode() == 1
             and _sw.ab("SCAT_S2_SPLIT", True)):
@@ -293,18 +287,18 @@ def _conv2d_fwd(x, w, stride, pad, in_scale=None, in_shift=None, in_relu=False, 
                          lib().scat_conv2d_fwd_split_ws(Cout, Cin, KH, KW), x.device)
         _prof(2.0 * B * OH * OW * Cout * Cin * KH * KW, lib().scat_conv2d_fwd_split, _p(x), _p(w), _p(bias), _p(y), B,
               Cin, H, W, Cout, KH, KW, stride, pad, _p(in_scale), _p(in_shift), int(in_relu), _p(ws), ws.numel(),
-              rdy, _stream())
+              rdy, epi, _stream())
         return y
     if (KH == 7 and KW == 7 and stride == 2 and pad == 3 and Cin == 3 and bias is None and in_scale is None
             and lib().scat_get_math_mode() == 1 and STEM_SPLIT):
         ws = workspace(lib().scat_conv7x7_s2_fwd_split_ws(Cout), x.device, "stem")
         _prof(2.0 * B * OH * OW * Cout * Cin * KH * KW, lib().scat_conv7x7_s2_fwd_split, _p(x), _p(w), _p(y), B, H, W,
-              Cout, _p(ws), ws.numel(), _stream())
+              Cout, _p(ws), ws.numel(), epi, _stream())
         return y
     if _halo_ok(KH, KW, stride, pad, Cin, W) and bias is None:
         ws, rdy = _wp_ws(wp, w, WPREP_CONV3X3_FWD, Cout, Cin, 3, 3, 1, lib().scat_conv3x3_s1_ws(Cout, Cin), x.device)
         _prof(2.0 * B * OH * OW * Cout * Cin * 9, lib().scat_conv3x3_s1, _p(x), _p(w), _p(y), B, Cin, H, W, Cout, 0,
-              _p(in_scale), _p(in_shift), int(in_relu), 0, _p(ws), ws.numel(), rdy, _stream())
+              _p(in_scale), _p(in_shift), int(in_relu), 0, _p(ws), ws.numel(), rdy, epi, _stream())
         return y
     _prof(2.0 * B * OH * OW * Cout * Cin * KH * KW, lib().scat_conv2d_fwd, _p(x), _p(w), _p(bias), _p(y), B, Cin, H, W,
           Cout, KH, KW, stride, pad, _p(in_scale), _p(in_shift), int(in_relu), _stream())
@@ -385,9 +379,26 @@ def conv2d_dgrad(dy, wt, x_shape, w_shape, stride, pad, out=None, accumulate=Fal
     return dx
 
 
-def conv2d_dgrad_w(dy, w, x_shape, stride, pad, out=None, accumulate=False, wp=None):
+def conv2d_dgrad_w(dy, w, x_shape, stride, pad, out=None, accumulate=False, wp=None, bnb=None):
     """Data gradient from the ORIGINAL weights: picks the parity-decomposed stride-2 kernels when they apply,
-    else transposes the weights and runs the generic gather."""
+    else transposes the weights and runs the generic gather.
+    bnb = (x, mask, mean): this accumulating call completes the gradient of relu(bn(x) + residual) — ask the pointwise
+    kernel to mask it with ``mask`` and leave the BatchNorm backward's two sums per channel (include/scat_hip.h
+    ScatEpilogue); ``dx.scat_bnb`` = (partials, groups) when it did, for ``bn_bwd_pre_partials``, else None."""
+    if bnb is None:
+        return _conv2d_dgrad_w(dy, w, x_shape, stride, pad, out, accumulate, wp)
+    x, mask, mean = bnb
+    _chk(x, mean)
+    B, C, H, W = x.shape
+    nbytes = C * ((B * H * W + 31) // 32 + 4) * 8
+    part = workspace(nbytes, x.device, "bnbpart")
+    epi = _Epilogue(_p(part), nbytes, 0, 0, _p(x), _p(mask), _p(mean))
+    dx = _conv2d_dgrad_w(dy, w, x_shape, stride, pad, out, accumulate, wp, epi)
+    dx.scat_bnb = (part, epi.groups) if epi.groups > 0 else None
+    return dx
+
+
+def _conv2d_dgrad_w(dy, w, x_shape, stride, pad, out=None, accumulate=False, wp=None, epi=None):
     _chk(dy, w, out)
     B, Cin, H, W = x_shape
     Cout, _, KH, KW = w.shape
@@ -406,13 +417,13 @@ def conv2d_dgrad_w(dy, w, x_shape, stride, pad, out=None, accumulate=False, wp=N
         dx = out if out is not None else torch.empty(x_shape, dtype=torch.float32, device=dy.device)
         ws, rdy = _wp_ws(wp, w, WPREP_CONV3X3_DGRAD, Cout, Cin, 3, 3, 1, lib().scat_conv3x3_s1_ws(Cout, Cin), dy.device)
         _prof(2.0 * B * H * W * Cout * Cin * 9, lib().scat_conv3x3_s1, _p(dy), _p(w), _p(dx), B, Cin, H, W, Cout, 1,
-              0, 0, 0, int(accumulate), _p(ws), ws.numel(), rdy, _stream())
+              0, 0, 0, int(accumulate), _p(ws), ws.numel(), rdy, 0, _stream())
         return dx
     if _pw_ok(KH, KW, stride, pad, Cout, dy, w, out):
         dx = out if out is not None else torch.empty(x_shape, dtype=torch.float32, device=dy.device)
         ws, rdy = _wp_ws(wp, w, WPREP_CONV1X1_DGRAD, Cout, Cin, 1, 1, 0, lib().scat_conv1x1_s1_ws(Cin, Cout), dy.device)
         _prof(2.0 * B * H * W * Cout * Cin, lib().scat_conv1x1_s1, _p(dy), _p(w), _p(dx), B, Cout, H * W, Cin, 1, 0, 0,
-              0, 0, int(accumulate), _p(ws), ws.numel(), rdy, _stream())
+              0, 0, int(accumulate), _p(ws), ws.numel(), rdy, 0 if epi is None else ctypes.addressof(epi), _stream())
         return dx
     wt = conv2d_wt(w, out=workspace(4 * w.numel(), dy.device, "wt")[: 4 * w.numel()].view(torch.float32)
                    .view(Cin, Cout * KH * KW))
@@ -513,6 +524,12 @@ class _GemmProblem(ctypes.Structure):
                 ("b", ctypes.c_void_p), ("b_sk", ctypes.c_int64), ("b_sj", ctypes.c_int64),
                 ("c", ctypes.c_void_p), ("c_si", ctypes.c_int64), ("c_sj", ctypes.c_int64),
                 ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int)]
+
+
+class _Epilogue(ctypes.Structure):
+    """include/scat_hip.h ScatEpilogue: one convolution call's request for BatchNorm sums; ``groups`` comes back"""
+    _fields_ = [("part", ctypes.c_void_p), ("part_bytes", ctypes.c_int64), ("groups", ctypes.c_int),
+                ("shift", ctypes.c_void_p), ("x", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("mean", ctypes.c_void_p)]
 
 
 GROUP_WGRAD = _sw.ab("SCAT_GROUP_WGRAD", True)   # the token mixer's weight gradients as one launch
@@ -698,24 +715,8 @@ def bn_bwd_pre(dy, x, relu, scale, shift, save_mean, save_invstd, gamma, dgamma=
     return coef3, dgamma, dbeta
 
 
-def epilogue_bnb_arm(x, mask, mean):
-    """Arm the next accumulating pointwise data gradient on this host thread (include/scat_hip.h scat_epilogue_bnb_arm): it
-    completes the gradient of relu(bn(x) + residual); its epilogue masks it with ``mask`` and leaves the BatchNorm
-    backward's two sums per channel.  -> the partials' workspace (pass it to bn_bwd_pre_partials with epilogue_bnb_groups())."""
-    _chk(x, mean)
-    B, C, H, W = x.shape
-    nbytes = C * ((B * H * W + 31) // 32 + 4) * 8
-    part = workspace(nbytes, x.device, "bnbpart")
-    lib().scat_epilogue_bnb_arm(_p(x), _p(mask), _p(mean), x.numel(), _p(part), nbytes)
-    return part
-
-
-def epilogue_bnb_groups():
-    return lib().scat_epilogue_bnb_groups()
-
-
 def bn_bwd_pre_partials(part, groups, x_shape, save_mean, save_invstd, gamma, dgamma=None, dbeta=None):
-    """(coef3, dgamma, dbeta) of bn_bwd_pre from the sums an armed data-gradient epilogue left (the masked gradient is in place)"""
+    """(coef3, dgamma, dbeta) of bn_bwd_pre from the sums conv2d_dgrad_w(bnb=...) left (the masked gradient is in place)"""
     _chk(save_mean, save_invstd, gamma, dgamma, dbeta)
     B, C, H, W = x_shape
     dgamma = dgamma if dgamma is not None else torch.empty_like(gamma)

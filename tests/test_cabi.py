@@ -19,6 +19,11 @@ def built():
     return build.build(verbose=False)
 
 
+# the per-thread request protocol that ScatEpilogue replaced: declared and exported nowhere
+ARM_STATE = ("scat_epilogue_stats_arm", "scat_epilogue_stats_arm_shift", "scat_epilogue_stats_groups",
+             "scat_epilogue_bnb_arm", "scat_epilogue_bnb_groups")
+
+
 def test_header_declares_the_path():
     from scat_amd._lib import parse_header
 
@@ -32,13 +37,13 @@ def test_header_declares_the_path():
     # every data-path entry point is stream-ordered: last argument is the stream
     for name, (rt, args) in protos.items():
         if rt is ctypes.c_int and name not in ("scat_version", "scat_check_device", "scat_get_math_mode",
-                                                "scat_set_math_mode",
-                                                # host-side state of the NEXT launch of this thread, no device work
-                                                "scat_epilogue_stats_arm", "scat_epilogue_stats_arm_shift", "scat_epilogue_stats_groups",
-                                                "scat_epilogue_bnb_arm", "scat_epilogue_bnb_groups"):
+                                                "scat_set_math_mode"):
             assert args[-1][1] == "stream", name
-    # every prototype cites the reference file it replaces somewhere in the header
     src = open(os.path.join(ROOT, "include", "scat_hip.h")).read()
+    # an epilogue request travels with its call (ScatEpilogue): no entry point keeps one for the next launch
+    for name in ARM_STATE:
+        assert name not in protos and name not in src, name
+    # every prototype cites the reference file it replaces somewhere in the header
     assert len(re.findall(r"models/\w+\.py:\d+|train\.py:\d+|hand_net\.py:\d+", src)) >= 12
 
 
@@ -49,7 +54,7 @@ def test_library_exports_every_symbol(built):
     for name in parse_header():
         assert hasattr(L.cdll, name), name
         assert "streamk" not in name, name
-    for name in ("scat_streamk_bytes", "scat_streamk_arm", "scat_streamk_error"):
+    for name in ("scat_streamk_bytes", "scat_streamk_arm", "scat_streamk_error") + ARM_STATE:
         assert not hasattr(L.cdll, name), name
     assert L.scat_version() >= 100
     assert isinstance(L.scat_last_kernel(), bytes)
@@ -268,3 +273,59 @@ def test_sufficient_and_unused_workspaces_pass_validation(name, built):
                                  (WS_PTR + 2, need, "_split1"), (WS_PTR, need, "_split3")):
             rc, err, _, label = e(ws, nbytes)
             assert rc == -4 and label.decode().endswith(want), (ws, nbytes, rc, err, label)
+
+
+# ------------------------------------------------------------------ the epilogue request (include/scat_hip.h ScatEpilogue)
+
+EPI_ENTRIES = ("scat_conv1x1_s1", "scat_conv3x3_s1", "scat_conv2d_fwd_split", "scat_conv7x7_s2_fwd_split")
+
+
+def test_epilogue_descriptor_mirror_has_the_librarys_size(built):
+    from scat_amd import ops
+    from scat_amd._lib import lib
+
+    assert ctypes.sizeof(ops._Epilogue) == lib().scat_epilogue_bytes() == 56
+
+
+@pytest.mark.parametrize("name", EPI_ENTRIES)
+def test_a_refused_call_reports_zero_groups(name, built):
+    """groups is written before the first check: a caller that reads it after a refusal never sees a stale count"""
+    from scat_amd import ops
+    from scat_amd._lib import HostInOut
+
+    e = _Entry(name)
+    assert [an for _, an in e.L.protos[name][1]][-2:] == ["epi", "stream"]
+    # host memory, dereferenced before the first check: bound as its own type, which ws_call_args leaves null
+    assert [an for ty, an in e.L.protos[name][1] if ty is HostInOut] == ["epi"]
+    assert e.G.ws_call_args(e.L, name, e.row.shape, 0, 0)[-2:] == [0, 0]
+    epi = ops._Epilogue(0x5000000, 1 << 20, 77)
+    rc, err, before, after = e(WS_PTR, e.need() - 1, dict(e.row.shape, epi=ctypes.addressof(epi)))
+    assert rc == -3 and name in err, (rc, err)
+    assert epi.groups == 0
+    assert before == after, f"{name}: refused, yet the kernel label moved to {after}"
+
+
+def test_the_request_is_decided_by_its_own_call(built):
+    """scat_conv1x1_s1 forward, 64 rows x 234 pixels on 64 x 128 tiles of two column groups each: 4 groups.  The capacity
+    rule (rows * groups * 8 <= part_bytes, else not done) and the bias rule, as far as the launch (-4: no device)"""
+    _no_device()
+    from scat_amd import ops
+
+    e = _Entry("scat_conv1x1_s1")
+    shape = dict(B=2, C=128, HW=117, M=64)
+    need = e.need(shape)
+    saved = e.L.scat_get_math_mode()
+    e.L.scat_set_math_mode(1)
+    try:
+        def groups(part_bytes, null):
+            epi = ops._Epilogue(0x5000000, part_bytes, 77)
+            rc, err, _, label = e(WS_PTR, need, dict(shape, epi=ctypes.addressof(epi)), null)
+            assert rc == -4 and label.startswith(b"conv1x1_split_64x128x32"), (rc, err, label)
+            return epi.groups
+        g = groups(1 << 20, ("bias",))
+        assert g == 4
+        assert groups(64 * g * 8, ("bias",)) == g
+        assert groups(64 * g * 8 - 1, ("bias",)) == 0
+        assert groups(1 << 20, ()) == 0                     # a bias: the statistics would not be the convolution's
+    finally:
+        e.L.scat_set_math_mode(saved)

@@ -37,7 +37,7 @@ def test_eval_header_is_bound_beside_the_main_one(built):
     # the default parse is still the main header alone: none of the evaluation names, nothing lost
     main = parse_header()
     assert not set(main) & set(protos)
-    assert len(main) == 95 and {"scat_loss_fwd_bwd", "scat_augment_plan", "scat_version"} <= set(main)
+    assert len(main) == 91 and {"scat_loss_fwd_bwd", "scat_augment_plan", "scat_version"} <= set(main)
     assert set(L.protos) == set(main) | set(protos)
     src = open(EVAL_H).read()
     assert src.count("eval.py:") >= 8      # every entry point cites the reference lines it stands in for

@@ -215,7 +215,8 @@ def ws_query(L, name, args):
 
 def ws_call_args(L, name, shape, ws, ws_bytes, null=()):
     """positional arguments of entry point ``name`` at ``shape`` for a call that is to stop in the host code (no GPU):
-    distinct non-null 16-byte-aligned integers as pointers (null for row.null and ``null``), 0 for flags and the stream"""
+    distinct non-null 16-byte-aligned integers as pointers (null for row.null and ``null``), 0 for flags and the stream,
+    and null for ``epi`` (HOST memory that the entry point reads and writes) unless ``shape`` brings a real one"""
     row = WS[name]
     vals = dict(shape)
     if row.build:
@@ -227,7 +228,7 @@ def ws_call_args(L, name, shape, ws, ws_bytes, null=()):
         elif an in vals:
             out.append(vals[an])
         elif ty is ctypes.c_void_p:
-            out.append(0 if an in row.null or an in null or an == "stream" else 0x100000 * (n + 1))
+            out.append(0 if an in row.null or an in null or an in ("stream", "epi") else 0x100000 * (n + 1))
         else:
             out.append(0.125 if ty is ctypes.c_float else 0)
     return out
@@ -585,8 +586,8 @@ def _c14(t):
 
 # BatchNorm sums in the forward epilogue.  S / O: the pointwise and halo kernels still run for the 3x3 and stride-2 cases;
 # where the general engine takes over the call reports 0 groups and bn_train_stats takes its pass over y: same numbers.
-@case("conv_epilogue_stats", ("scat_epilogue_stats_arm", "scat_epilogue_stats_arm_shift", "scat_bn_train_stats_partials",
-                              "scat_bn_train_stats_partials_shifted", "scat_conv1x1_s1", "scat_conv3x3_s1"), 2e-5, maths=(1,))
+@case("conv_epilogue_stats", ("scat_bn_train_stats_partials", "scat_bn_train_stats_partials_shifted", "scat_conv1x1_s1",
+                              "scat_conv3x3_s1"), 2e-5, maths=(1,))
 def _c15(t):
     for B, cin, cout, k, H, W in ((2, 128, 64, 1, 13, 9), (2, 32, 32, 3, 11, 9)):
         key = f"k{k}"
@@ -927,10 +928,10 @@ def bn3_reference(c3, res_sign, gamma, mean, invstd, g_old, dc1, w1):
     return g, torch.stack((ca, cb, cc)), dg, db
 
 
-# the armed bn3 epilogue at a channel count with a partial 128-row tile.  A: the accumulating pointwise data gradient
-# masks, stores and leaves the sums.  S / O: ops._pw_ok sends a skewed dy / w / out to the general engine, which ignores
-# the arm (0 groups), and the protocol's fallback, scat_bn_bwd_pre, rejects the skewed gradient with SCAT_E_SHAPE.
-@case("bn3_epilogue_ragged_c", ("scat_epilogue_bnb_arm", "scat_bn_bwd_pre_partials", "scat_conv1x1_s1"), 2e-5,
+# the bn3 epilogue at a channel count with a partial 128-row tile.  A: the accumulating pointwise data gradient masks,
+# stores and leaves the sums.  S / O: ops._pw_ok sends a skewed dy / w / out to the general engine, which takes no
+# request (no groups), and the caller's fallback, scat_bn_bwd_pre, rejects the skewed gradient with SCAT_E_SHAPE.
+@case("bn3_epilogue_ragged_c", ("scat_bn_bwd_pre_partials", "scat_conv1x1_s1"), 2e-5,
       expect={"S": "SCAT_E_SHAPE", "O": "SCAT_E_SHAPE"}, direct=True, maths=(1,))
 def _b10(t):
     B, C, K, H = 3, 320, 64, 28
@@ -953,12 +954,10 @@ def _b10(t):
     ref = lambda i: (lambda: t.once("bn3ref", lambda: bn3_reference(c3, sign, gamma, mean, invstd, g_old, dc1, w1))[i])
     c3g, maskg, meang = t.inp(c3, "c3"), t.inp(t.once("mask", mask_bytes), "mask"), t.inp(mean, "mean")
     invg, gammag = t.inp(invstd, "invstd"), t.inp(gamma, "gamma")
-    part = ops.epilogue_bnb_arm(c3g, maskg, meang)
     new = t.acc(g_old, "g")
-    try:
-        ops.conv2d_dgrad_w(t.inp(dc1, "dc1"), t.inp(w1, "w1"), (B, C, H, H), 1, 0, out=new, accumulate=True)
-    finally:
-        groups = ops.epilogue_bnb_groups()
+    ops.conv2d_dgrad_w(t.inp(dc1, "dc1"), t.inp(w1, "w1"), (B, C, H, H), 1, 0, out=new, accumulate=True,
+                       bnb=(c3g, maskg, meang))
+    part, groups = new.scat_bnb or (None, 0)
     if t.aligned:
         assert groups > 0 and t.label().endswith("_epibn"), (groups, t.label())
     if groups > 0:

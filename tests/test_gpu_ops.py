@@ -586,6 +586,71 @@ def test_conv_epilogue_statistics_with_large_channel_offsets(ops, k, cin, cout, 
         assert e_plain[1] > 10 * e_ref[1], (e_ref, e_plain)           # the reference is what makes the difference
 
 
+# the small shapes of tests/test_gpu_guard.py conv_epilogue_stats: ragged last tiles on the pointwise and the halo kernel
+EPI_PW, EPI_3X3 = (2, 128, 64, 1, 13, 9), (2, 32, 32, 3, 11, 9)
+
+
+def _epi_conv(ops, shape, seed, bias=None, sentinel=-7.5):
+    """one forward convolution at the C level with a ScatEpilogue over the test's own partials buffer
+    -> (y, fp64 reference of the convolution without bias, the descriptor, the partials pre-filled with ``sentinel``)"""
+    import ctypes
+
+    L, P = ops.lib(), (lambda a: 0 if a is None else a.data_ptr())
+    B, cin, cout, k, H, W = shape
+    x = t(seed, "x", (B, cin, H, W)) * 1.3 + 0.2
+    w = t(seed + 1, "w", (cout, cin, k, k), std=(2.0 / (cin * k * k)) ** 0.5)
+    xg, wg, y = g(x), g(w), torch.empty((B, cout, H, W), device=DEV)
+    part = torch.full((cout * ((B * H * W + 31) // 32 + 4) * 2,), sentinel, device=DEV)
+    epi = ops._Epilogue(P(part), part.numel() * 4, 77)
+    if k == 1:
+        ws = torch.empty(L.scat_conv1x1_s1_ws(cout, cin), dtype=torch.uint8, device=DEV)
+        L.scat_conv1x1_s1(P(xg), P(wg), P(y), B, cin, H * W, cout, 0, P(bias), 0, 0, 0, 0, P(ws), ws.numel(), 0,
+                          ctypes.addressof(epi), ops._stream())
+    else:
+        ws = torch.empty(L.scat_conv3x3_s1_ws(cout, cin), dtype=torch.uint8, device=DEV)
+        L.scat_conv3x3_s1(P(xg), P(wg), P(y), B, cin, H, W, cout, 0, 0, 0, 0, 0, P(ws), ws.numel(), 0,
+                          ctypes.addressof(epi), ops._stream())
+    return y, F.conv2d(x.double(), w.double(), padding=k // 2), epi, part
+
+
+def test_an_epilogue_request_belongs_to_its_call(ops, math_mode):
+    """Two convolutions, each with its own ScatEpilogue, then a contraction that offers none (scat_gemm_split: a
+    non-accumulating, bias-less launch of the same kernel family), then the two sets of statistics finished in the
+    reverse order: each request was served by its own call, and the contraction in between touched neither buffer."""
+    math_mode(1)
+    L, P = ops.lib(), (lambda a: a.data_ptr())
+    ya, ra, ea, pa = _epi_conv(ops, EPI_PW, 81)
+    yb, rb, eb, pb = _epi_conv(ops, EPI_3X3, 83)
+    assert ea.groups > 0 and eb.groups > 0, (ea.groups, eb.groups)
+    before = (pa.clone(), pb.clone())
+    a, b, c = g(t(85, "a", (64, 64))), g(t(86, "b", (64, 64))), torch.empty((64, 64), device=DEV)
+    ws = torch.empty(L.scat_gemm_split_ws(64, 64), dtype=torch.uint8, device=DEV)
+    L.scat_gemm_split(P(a), 0, P(b), P(c), 64, 64, 64, 0, 0, P(ws), ws.numel(), ops._stream())
+    assert rel_err(c, t(85, "a", (64, 64)).double() @ t(86, "b", (64, 64)).double()) < 2e-5
+    assert torch.equal(pa, before[0]) and torch.equal(pb, before[1])
+    for (B, _, cout, _, H, W), y, ref, epi, part in ((EPI_3X3, yb, rb, eb, pb), (EPI_PW, ya, ra, ea, pa)):
+        assert rel_err(y, ref) < 2e-5
+        gamma, beta, rm, rv = (torch.ones(cout, device=DEV), torch.zeros(cout, device=DEV),
+                               torch.zeros(cout, device=DEV), torch.ones(cout, device=DEV))
+        o = torch.empty((4, cout), device=DEV)
+        L.scat_bn_train_stats_partials(P(part), epi.groups, B, cout, H * W, P(gamma), P(beta), P(rm), P(rv), 0.1, 1e-5,
+                                       P(o[0]), P(o[1]), P(o[2]), P(o[3]), ops._stream())
+        e_mean = rel_err(o[0], ref.mean(dim=(0, 2, 3)))
+        e_invstd = rel_err(o[1], 1.0 / torch.sqrt(ref.var(dim=(0, 2, 3), unbiased=False) + 1e-5))
+        print(f"epilogue request k{3 if H == 11 else 1}: groups {epi.groups} mean {e_mean:.2e} invstd {e_invstd:.2e}")
+        assert e_mean < 2e-5 and e_invstd < 2e-5
+
+
+def test_a_convolution_with_bias_leaves_an_epilogue_request_alone(ops, math_mode):
+    """the sums would be those of y - bias: the call reports 0 groups and does not touch the partials"""
+    math_mode(1)
+    bias = t(88, "bias", (EPI_PW[2],))
+    y, ref, epi, part = _epi_conv(ops, EPI_PW, 81, bias=g(bias), sentinel=-7.5)
+    assert epi.groups == 0
+    assert bool((part == -7.5).all())
+    assert rel_err(y, ref + bias.double().view(1, -1, 1, 1)) < 2e-5
+
+
 def test_batchnorm_sign_mask(ops):
     """bn_bwd from the 1-bit sign mask of the block output == bn_bwd from the output itself, bit for bit."""
     B, C, H = 3, 64, 28
@@ -1421,7 +1486,7 @@ def test_conv1x1_planes_bit_identical(ops, cin, cout, H, B):
                                      (96, 256, 64, 56)])                       # the benchmarked size (layer1 -> layer2)
 def test_bn_backward_sums_in_the_data_gradient_epilogue(ops, B, C, K, H):
     """The gradient of a Bottleneck output is completed by the next block's conv1 data gradient, accumulated onto the
-    shortcut's gradient (models/resnet.py:93-96).  Armed (scat_epilogue_bnb_arm), that kernel's epilogue applies the
+    shortcut's gradient (models/resnet.py:93-96).  Asked to (ScatEpilogue x / mask / mean), that kernel's epilogue applies the
     output's sign mask and leaves bn3's backward sums: the masked gradient must be bit for bit what the accumulate followed
     by scat_bn_bwd_pre writes, coef3 / d-gamma / d-beta the same to rounding (fp32 tile sums, then fp64).
 
@@ -1448,19 +1513,20 @@ def test_bn_backward_sums_in_the_data_gradient_epilogue(ops, B, C, K, H):
     # reference: accumulate, then the reduction pass
     ref = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True)
     coef_r, dg_r, db_r = ops.bn_bwd_pre(ref, c3, True, scale, shift, mean, invstd, gamma, y_mask=mask)
-    # armed epilogue
-    part = ops.epilogue_bnb_arm(c3, mask, mean)
-    new = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True)
-    groups = ops.epilogue_bnb_groups()
+    # the same call with the request
+    new = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True, bnb=(c3, mask, mean))
+    assert new.scat_bnb is not None, ops.lib().scat_last_kernel()
+    part, groups = new.scat_bnb
     assert groups > 0 and ops.lib().scat_last_kernel().decode().endswith("_epibn"), ops.lib().scat_last_kernel()
     coef_n, dg_n, db_n = ops.bn_bwd_pre_partials(part, groups, (B, C, H, H), mean, invstd, gamma)
     assert torch.equal(new, ref)
     assert rel_err(dg_n, dg_r) < 1e-5 and rel_err(db_n, db_r) < 1e-5
     for k in range(3):
         assert rel_err(coef_n[k], coef_r[k]) < 1e-5
-    # the arm is one-shot: the next call is the plain accumulate again
+    # the request belonged to that call: the next one without it is the plain accumulate again
     again = ops.conv2d_dgrad_w(dc1, w1, (B, C, H, H), 1, 0, out=g_old.clone(), accumulate=True)
-    assert ops.epilogue_bnb_groups() == 0 and not torch.equal(again, ref)
+    assert getattr(again, "scat_bnb", None) is None and not ops.lib().scat_last_kernel().decode().endswith("_epibn")
+    assert not torch.equal(again, ref)
     del again, ref, res, g_old, dc1
     # ---- fp64, independent of the library's own unfused pair
     from test_gpu_guard import bn3_reference
