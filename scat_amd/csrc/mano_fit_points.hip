@@ -17,8 +17,15 @@
 // Static LDS at the largest sizes: 18 KiB of vertices, 32 KiB of indices, 2.6 KiB of pose state: 53 KiB of the 64.
 // scat_mano_fit_points launches {assign, scat_mano_fit_verts} `rounds` times and one last assign; each assign after the
 // first adds the accepted count of the fit before it to the caller's total.
+//
+// kPlane (include/scat_mano_fit_plane.h, point-to-plane ICP): the thread that owns vertex v in the reduction first forms
+// the vertex normal from the LDS model points and the topology in global memory (mesh_vertex_normal, fp64), keeps it in
+// registers, writes it to the caller, and adds rho instead of d2 to the data cost; W, S, the walk and the index array do
+// not know, so every other output keeps the bits of the plain form.  No LDS is added.  mesh_normals_kernel is the same
+// function on the caller's vertices.  scat_mano_fit_points_plane is the loop with scat_mano_fit_verts_metric.
 #include "mano_fit_common.h"
 
+#include "../../include/scat_mano_fit_plane.h"
 #include "../../include/scat_mano_fit_points.h"
 
 namespace scat {
@@ -47,6 +54,13 @@ struct CloudArgs {
     float* data_cost;
     int fold;
     int N, V;
+    // kPlane (scat_mano_fit_plane.h): the topology, the normals of the model points, tau
+    const int32_t* faces;
+    const int32_t* vf_off;
+    const int32_t* vf_idx;
+    float* normals;        // [B,V,3]
+    float w_tangent;
+    int F;
 };
 
 template <bool kParams>
@@ -62,6 +76,42 @@ __device__ __forceinline__ double cloud_d2(double qx, double qy, double qz, doub
 #pragma clang fp contract(off)
     const double dx = qx - x, dy = qy - y, dz = qz - z;
     return (dx * dx + dy * dy) + dz * dz;
+}
+
+// kPlane, the metric data cost of a matched point: d2 its squared distance, (rx, ry, rz) = q - x, n the vertex normal as
+// rounded to fp32 (not zero), tau the tangential weight.  scat_mano_fit_plane.h's rho, every product and sum rounded once
+__device__ __forceinline__ double cloud_rho(double d2, double rx, double ry, double rz, const double (&n)[3], double tau) {
+#pragma clang fp contract(off)
+    const double nr = (n[0] * rx + n[1] * ry) + n[2] * rz;
+    return tau * d2 + (1.0 - tau) * (nr * nr);
+}
+
+// The normal of vertex v of the mesh mp (x / y / z arrays) by scat_mano_fit_plane.h's rule: the cross products of the
+// incident faces in vf_idx order and their sum in fp64 on the fp32 numbers, every product and sum rounded once, the
+// quotients rounded to fp32 once.  A corrupt index skips the face; no read leaves faces[3 F], vf_off[V + 1], vf_idx[3 F]
+__device__ __forceinline__ void mesh_vertex_normal(const float (*mp)[kMMaxV], const int32_t* faces, const int32_t* vf_off,
+                                                   const int32_t* vf_idx, int V, int F, int v, float (&n)[3]) {
+#pragma clang fp contract(off)
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    const int k0 = max(vf_off[v], 0), k1 = min(vf_off[v + 1], 3 * F);
+    for (int k = k0; k < k1; ++k) {
+        const int f = vf_idx[k];
+        if (f < 0 || f >= F) continue;
+        const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
+        if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) continue;
+        const double ax = (double)mp[0][ia], ay = (double)mp[1][ia], az = (double)mp[2][ia];
+        const double ux = (double)mp[0][ib] - ax, uy = (double)mp[1][ib] - ay, uz = (double)mp[2][ib] - az;
+        const double wx = (double)mp[0][ic] - ax, wy = (double)mp[1][ic] - ay, wz = (double)mp[2][ic] - az;
+        sx += uy * wz - uz * wy;
+        sy += uz * wx - ux * wz;
+        sz += ux * wy - uy * wx;
+    }
+    const double l2 = (sx * sx + sy * sy) + sz * sz;
+    const bool ok = l2 > 0.0 && l2 < __builtin_huge_val();   // not zero, not NaN, not inf
+    const double l = sqrt(l2);
+    n[0] = ok ? (float)(sx / l) : 0.f;
+    n[1] = ok ? (float)(sy / l) : 0.f;
+    n[2] = ok ? (float)(sz / l) : 0.f;
 }
 
 // each of NQ points against all V vertices, ascending; the vertex address is wave-uniform
@@ -101,8 +151,13 @@ __device__ __forceinline__ void cloud_unusable(const CloudArgs& a, int64_t b, bo
     }
 }
 
+// the normals of a hand that is not assigned (kPlane).  All threads
+__device__ __forceinline__ void cloud_zero_normals(const CloudArgs& a, int64_t b) {
+    for (int i = threadIdx.x; i < 3 * a.V; i += kFThreads) a.normals[b * 3 * a.V + i] = 0.f;
+}
+
 // grid = B, block = 256
-template <bool kParams>
+template <bool kParams, bool kPlane = false>
 __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
     __shared__ float mp[3][kMMaxV];      // the model points, x / y / z
     __shared__ alignas(16) int sidx[kPMaxN];   // the vertex of a matched point, -1 otherwise; read four at a time
@@ -125,6 +180,7 @@ __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
     }
     if (__syncthreads_or(bad)) {   // the same for every thread of the workgroup
         cloud_unusable(a, b, true);
+        if constexpr (kPlane) cloud_zero_normals(a, b);
         return;
     }
 
@@ -163,6 +219,7 @@ __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
     }
     if (__syncthreads_or(bad)) {   // (also the barrier that publishes mp)
         cloud_unusable(a, b, false);
+        if constexpr (kPlane) cloud_zero_normals(a, b);
         return;
     }
 
@@ -207,12 +264,30 @@ __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
         const double x = (double)mp[0][v], y = (double)mp[1][v], z = (double)mp[2][v];
         double W = 0.0, S[3] = {0.0, 0.0, 0.0}, C = 0.0;
         int cnt = 0;
+        // kPlane: this vertex's normal from the LDS model points, into registers and to the caller, before the scan
+        double nv[3] = {0.0, 0.0, 0.0};
+        bool flat = true;
+        if constexpr (kPlane) {
+            float n[3];
+            mesh_vertex_normal(mp, a.faces, a.vf_off, a.vf_idx, V, a.F, v, n);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                a.normals[(b * V + v) * 3 + c] = n[c];
+                nv[c] = (double)n[c];
+            }
+            flat = n[0] == 0.f && n[1] == 0.f && n[2] == 0.f;
+        }
         const auto take = [&](int n) {
             const double w = wts ? (double)wts[n] : 1.0;
             const double q0 = (double)pts[3 * n], q1 = (double)pts[3 * n + 1], q2 = (double)pts[3 * n + 2];
             W += w;
             S[0] += w * q0, S[1] += w * q1, S[2] += w * q2;   // fp32 x fp32: the products are exact in fp64
-            C += w * cloud_d2(q0, q1, q2, x, y, z);
+            if constexpr (kPlane) {
+                const double d2 = cloud_d2(q0, q1, q2, x, y, z);
+                C += w * (flat ? d2 : cloud_rho(d2, q0 - x, q1 - y, q2 - z, nv, (double)a.w_tangent));
+            } else {
+                C += w * cloud_d2(q0, q1, q2, x, y, z);
+            }
             ++cnt;
         };
         // four indices per LDS read, two reads in flight: one index per read made a scan 130 cycles per point, the
@@ -256,6 +331,28 @@ __global__ __launch_bounds__(kFThreads) void cloud_assign_kernel(CloudArgs a) {
     }
 }
 
+// scat_mesh_normals: the caller's vertices into LDS, then mesh_vertex_normal per vertex.  grid = B, block = 256
+__global__ __launch_bounds__(kFThreads) void mesh_normals_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                                 const int32_t* __restrict__ vf_off,
+                                                                 const int32_t* __restrict__ vf_idx, float* __restrict__ normals,
+                                                                 int V, int F) {
+    __shared__ float mp[3][kMMaxV];
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* vs = verts + b * 3 * (int64_t)V;
+    for (int i = tid; i < 3 * V; i += kFThreads) {
+        const int v = i / 3, c = i - 3 * v;
+        mp[c][v] = vs[i];
+    }
+    __syncthreads();
+    for (int v = tid; v < V; v += kFThreads) {
+        float n[3];
+        mesh_vertex_normal(mp, faces, vf_off, vf_idx, V, F, v, n);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) normals[(b * V + v) * 3 + c] = n[c];
+    }
+}
+
 }  // namespace scat
 
 using namespace scat;
@@ -271,9 +368,9 @@ static int cloud_check(const char* fn, const void* const* nullable, int nn, cons
     return SCAT_OK;
 }
 
-template <bool kParams>
+template <bool kParams, bool kPlane = false>
 static int cloud_launch(const char* fn, const CloudArgs& a, int B, void* stream) {
-    hipLaunchKernelGGL(cloud_assign_kernel<kParams>, dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((cloud_assign_kernel<kParams, kPlane>), dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
     SCAT_LAUNCH_CHECK(fn);
     return SCAT_OK;
 }
@@ -350,12 +447,45 @@ extern "C" int64_t scat_mano_fit_points_ws(int B, int N, int V) {
     return points_ws(B, N, V).total;
 }
 
-extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
-                                    const float* hands_mean, const float* points, const float* weights, float* p,
-                                    float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
-                                    int N, int V, uint64_t parents, int rounds, int iters, float max_dist, float lambda0,
-                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
-    const char* fn = "scat_mano_fit_points";
+// the plane loop's workspace: scat_mano_fit_points' parts, then the normals [B,V,3]
+static int64_t plane_ws_total(int64_t B, int64_t N, int64_t V) {
+    return points_ws(B, N, V).total + ((B * V * 3 * (int64_t)sizeof(float) + 15) & ~(int64_t)15);
+}
+
+extern "C" int64_t scat_mano_fit_points_plane_ws(int B, int N, int V, int F) {
+    if (B < 1 || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV || F < 1 || F > SCAT_RENDER_MAX_F) return 0;
+    return plane_ws_total(B, N, V);
+}
+
+// the topology of a plane entry point: the three arrays present and aligned, F in range, tau in 0..1
+struct CloudTopo {
+    const int32_t* faces;
+    const int32_t* vf_off;
+    const int32_t* vf_idx;
+    int F;
+    float w_tangent;
+};
+
+static int topo_check(const char* fn, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, int F) {
+    SCAT_REQUIRE(faces && vf_off && vf_idx, SCAT_E_ARG, "%s: null pointer", fn);
+    SCAT_REQUIRE((((uintptr_t)faces | (uintptr_t)vf_off | (uintptr_t)vf_idx) & 3) == 0, SCAT_E_ARG,
+                 "%s: int32 operands must be 4-byte aligned", fn);
+    SCAT_REQUIRE(F >= 1 && F <= SCAT_RENDER_MAX_F, SCAT_E_SHAPE, "%s: %d faces outside 1..%d", fn, F, SCAT_RENDER_MAX_F);
+    return SCAT_OK;
+}
+
+static int tau_check(const char* fn, float w_tangent) {
+    SCAT_REQUIRE(w_tangent >= 0.f && w_tangent <= 1.f, SCAT_E_ARG, "%s: w_tangent %g outside 0..1", fn, (double)w_tangent);
+    return SCAT_OK;
+}
+
+// Both ICP loops: the checks, then 2 rounds + 1 launches.  topo null: scat_mano_fit_points; otherwise the plane form,
+// whose workspace ends with the normals
+static int points_loop(const char* fn, const char* label, const CloudTopo* topo, const float* blend, const float* joint_t,
+                       const float* joint_s, const float* weights_t, const float* hands_mean, const float* points,
+                       const float* weights, float* p, float* data_cost, int* accepted, int* idx, float* dist, void* ws,
+                       int64_t ws_bytes, int B, int N, int V, uint64_t parents, int rounds, int iters, float max_dist,
+                       float lambda0, float w_pose, float w_beta, uint64_t free_mask, void* stream) {
     const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, points, p, data_cost, accepted};
     CloudArgs a = {};
     a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
@@ -364,6 +494,11 @@ extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, co
     const void* nullable[] = {weights, idx, dist};
     rc = cloud_check(fn, nullable, 3, nullptr, N, max_dist);
     if (rc != SCAT_OK) return rc;
+    if (topo) {
+        rc = topo_check(fn, topo->faces, topo->vf_off, topo->vf_idx, topo->F);
+        if (rc == SCAT_OK) rc = tau_check(fn, topo->w_tangent);
+        if (rc != SCAT_OK) return rc;
+    }
     SCAT_REQUIRE(rounds >= 1 && rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, rounds,
                  SCAT_FIT_POINTS_MAX_ROUNDS);
     rc = fit_check_solver(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
@@ -373,9 +508,10 @@ extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, co
     rc = fit_check_mask(fn, free_mask);
     if (rc != SCAT_OK) return rc;
     const PointsWs w = points_ws(B, N, V);
+    const int64_t need = topo ? plane_ws_total(B, N, V) : w.total;
     SCAT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "%s: the workspace must be a 16-byte-aligned pointer", fn);
-    SCAT_REQUIRE(ws_bytes >= w.total, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
-                 (long long)w.total);
+    SCAT_REQUIRE(ws_bytes >= need, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
+                 (long long)need);
     char* base = static_cast<char*>(ws);
     float* vtarget = reinterpret_cast<float*>(base + w.vtarget);
     float* vw = reinterpret_cast<float*>(base + w.vw);
@@ -386,16 +522,89 @@ extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, co
     a.dist = dist ? dist : reinterpret_cast<float*>(base + w.dist);
     a.vw = vw, a.vtarget = vtarget, a.stats = reinterpret_cast<double*>(base + w.stats);
     a.acc_round = acc_r, a.acc_total = accepted, a.N = N, a.V = V;
+    if (topo) {
+        a.faces = topo->faces, a.vf_off = topo->vf_off, a.vf_idx = topo->vf_idx, a.F = topo->F, a.w_tangent = topo->w_tangent;
+        a.normals = reinterpret_cast<float*>(base + w.total);
+    }
     for (int r = 0; r <= rounds; ++r) {
         a.fold = r == 0 ? 1 : 2;
         a.data_cost = r == rounds ? data_cost : nullptr;
-        rc = cloud_launch<true>(fn, a, B, stream);
+        rc = topo ? cloud_launch<true, true>(fn, a, B, stream) : cloud_launch<true>(fn, a, B, stream);
         if (rc != SCAT_OK) return rc;
         if (r == rounds) break;
-        rc = scat_mano_fit_verts(blend, joint_t, joint_s, weights_t, hands_mean, vtarget, vw, p, cost_r, acc_r, B, V, parents,
-                                 iters, 0, lambda0, w_pose, w_beta, free_mask, stream);
+        rc = topo ? scat_mano_fit_verts_metric(blend, joint_t, joint_s, weights_t, hands_mean, vtarget, vw, a.normals, p, cost_r,
+                                               acc_r, B, V, parents, iters, topo->w_tangent, lambda0, w_pose, w_beta, free_mask,
+                                               stream)
+                  : scat_mano_fit_verts(blend, joint_t, joint_s, weights_t, hands_mean, vtarget, vw, p, cost_r, acc_r, B, V, parents,
+                                        iters, 0, lambda0, w_pose, w_beta, free_mask, stream);
         if (rc != SCAT_OK) return rc;
     }
-    set_kernel_label("mano_fit_points_v%d_n%d_r%d_i%d", V, N, rounds, iters);
+    set_kernel_label(label, V, N, rounds, iters);
     return SCAT_OK;
 }
+
+extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                    const float* hands_mean, const float* points, const float* weights, float* p,
+                                    float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
+                                    int N, int V, uint64_t parents, int rounds, int iters, float max_dist, float lambda0,
+                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
+    return points_loop("scat_mano_fit_points", "mano_fit_points_v%d_n%d_r%d_i%d", nullptr, blend, joint_t, joint_s, weights_t,
+                       hands_mean, points, weights, p, data_cost, accepted, idx, dist, ws, ws_bytes, B, N, V, parents, rounds,
+                       iters, max_dist, lambda0, w_pose, w_beta, free_mask, stream);
+}
+
+extern "C" int scat_mano_fit_points_plane(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                          const float* hands_mean, const float* points, const float* weights,
+                                          const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, float* p,
+                                          float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
+                                          int N, int V, int F, uint64_t parents, int rounds, int iters, float max_dist,
+                                          float w_tangent, float lambda0, float w_pose, float w_beta, uint64_t free_mask,
+                                          void* stream) {
+    const CloudTopo topo = {faces, vf_off, vf_idx, F, w_tangent};
+    return points_loop("scat_mano_fit_points_plane", "mano_fit_points_plane_v%d_n%d_r%d_i%d", &topo, blend, joint_t, joint_s,
+                       weights_t, hands_mean, points, weights, p, data_cost, accepted, idx, dist, ws, ws_bytes, B, N, V, parents,
+                       rounds, iters, max_dist, lambda0, w_pose, w_beta, free_mask, stream);
+}
+
+extern "C" int scat_mano_cloud_assign_plane(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                            const float* hands_mean, const float* p, const float* points, const float* weights,
+                                            const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, float max_dist,
+                                            float w_tangent, float* model_pts, float* normals, int* idx, float* dist, float* vw,
+                                            float* vtarget, double* stats, int B, int N, int V, int F, uint64_t parents,
+                                            void* stream) {
+    const char* fn = "scat_mano_cloud_assign_plane";
+    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, p, points, normals, idx, dist, vw, vtarget, stats};
+    CloudArgs a = {};
+    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
+    int rc = mano_validate(fn, ptrs, 13, B, V, parents, kNoTips, &a.m.levels);
+    if (rc != SCAT_OK) return rc;
+    const void* nullable[] = {weights, model_pts};
+    rc = cloud_check(fn, nullable, 2, stats, N, max_dist);
+    if (rc == SCAT_OK) rc = topo_check(fn, faces, vf_off, vf_idx, F);
+    if (rc == SCAT_OK) rc = tau_check(fn, w_tangent);
+    if (rc != SCAT_OK) return rc;
+    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist, a.model_pts = model_pts;
+    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
+    a.faces = faces, a.vf_off = vf_off, a.vf_idx = vf_idx, a.F = F, a.w_tangent = w_tangent, a.normals = normals;
+    rc = cloud_launch<true, true>(fn, a, B, stream);
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label("mano_cloud_assign_plane_v%d_n%d_f%d", V, N, F);
+    return SCAT_OK;
+}
+
+extern "C" int scat_mesh_normals(const float* verts, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx,
+                                 float* normals, int B, int V, int F, void* stream) {
+    const char* fn = "scat_mesh_normals";
+    SCAT_REQUIRE(verts && normals, SCAT_E_ARG, "%s: null pointer", fn);
+    SCAT_REQUIRE((((uintptr_t)verts | (uintptr_t)normals) & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
+    const int rc = topo_check(fn, faces, vf_off, vf_idx, F);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(B > 0, SCAT_E_SHAPE, "%s: batch %d must be positive", fn, B);
+    SCAT_REQUIRE(V >= 1 && V <= kMMaxV, SCAT_E_SHAPE, "%s: %d vertices outside 1..%d", fn, V, kMMaxV);
+    hipLaunchKernelGGL(mesh_normals_kernel, dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, verts, faces, vf_off, vf_idx, normals,
+                       V, F);
+    SCAT_LAUNCH_CHECK(fn);
+    set_kernel_label("mesh_normals_v%d_f%d", V, F);
+    return SCAT_OK;
+}
+

@@ -17,8 +17,14 @@
 // walk (fp32 within a tile, the tiles' sums added in fp64).  Row 62 of that product is g.  The trial cost of a step is a
 // forward pass with mano_vertex, one vertex per thread.  The solver's steps are mano_fit_common.h's.  All sums run in an
 // order fixed by V.
+//
+// kMetric (include/scat_mano_fit_plane.h): the cost of a vertex is r^T M r, M = n n^T + tau (I - n n^T) with the caller's
+// normal n.  The work-item that wrote the columns of a vertex into the tile takes them through sqrt(M) = a I + (1 - a) n n^T
+// in place, three entries of a column at a time, before the tile's barrier: no barrier and no LDS is added, and the
+// accumulation, the solve and accept / commit do not know.  vfit_cost sums rho instead of |r|^2.
 #include "mano_fit_common.h"
 
+#include "../../include/scat_mano_fit_plane.h"
 #include "../../include/scat_mano_fit_verts.h"
 
 namespace scat {
@@ -325,7 +331,18 @@ struct VFitArgs {
     int iters, init;
     float lambda0, w_pose, w_beta;
     uint64_t free_mask;
+    const float* normals;   // kMetric: [B,V,3]
+    float w_tangent;        // kMetric: tau
 };
+
+// kMetric: the three entries c[0], c[ld], c[2 ld] of a column through a I + (1 - a) n n^T
+__device__ __forceinline__ void vfit_sqrt_metric(float* c, int ld, const float n[3], float a) {
+    const float c0 = c[0], c1 = c[ld], c2 = c[2 * ld];
+    const float k = (1.f - a) * ((n[0] * c0 + n[1] * c1) + n[2] * c2);
+    c[0] = a * c0 + k * n[0];
+    c[ld] = a * c1 + k * n[1];
+    c[2 * ld] = a * c2 + k * n[2];
+}
 
 struct VFitLds {
     float A[kFU + 1][kFU];   // lower triangle: the damped normal matrix, then its factor; row 62: g, then L^-1 g
@@ -406,9 +423,11 @@ __device__ void vfit_procrustes(const ManoPose& s, const ManoArgs& pm, const flo
 }
 
 // f.ct = the cost at pp (pm's parameters): a forward pass, one vertex per thread, each thread its vertices ascending, a
-// butterfly over the wavefront, the wavefronts pairwise, then the priors.  All threads; begins and ends with a barrier
+// butterfly over the wavefront, the wavefronts pairwise, then the priors.  All threads; begins and ends with a barrier.
+// kMetric: rho = tau |r|^2 + (1 - tau) (n . r)^2 for the normals nrm [V,3], |r|^2 where the normal is zero
+template <bool kMetric>
 __device__ void vfit_cost(JacLds& m, VFitLds& f, const ManoArgs& pm, const float* pp, const float* tgt, const float* wts,
-                          float w_pose, float w_beta) {
+                          float w_pose, float w_beta, const float* nrm, float tau) {
     const int tid = threadIdx.x, V = pm.V;
     vj_setup(m, pm, 0, false);
     const ManoPose& s = m.s;
@@ -426,7 +445,14 @@ __device__ void vfit_cost(JacLds& m, VFitLds& f, const ManoArgs& pm, const float
         mv(Rg, d, x);
 #pragma unroll
         for (int a = 0; a < 3; ++a) r[a] = (sc * x[a] + tr[a]) - tgt[3 * v + a];
-        c += w * ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+        if constexpr (kMetric) {
+            const float n0 = nrm[3 * v], n1 = nrm[3 * v + 1], n2 = nrm[3 * v + 2];
+            const float r2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2], nr = (n0 * r[0] + n1 * r[1]) + n2 * r[2];
+            const bool flat = n0 == 0.f && n1 == 0.f && n2 == 0.f;
+            c += w * (flat ? r2 : tau * r2 + (1.f - tau) * (nr * nr));
+        } else {
+            c += w * ((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+        }
     }
     c = mano_wave_sum(c);
     if ((tid & 63) == 0) f.red[tid >> 6] = c;
@@ -443,8 +469,8 @@ __device__ void vfit_cost(JacLds& m, VFitLds& f, const ManoArgs& pm, const float
 }
 static_assert(kVWaves == 4, "vfit_cost adds four wavefronts");
 
-// grid = B, block = 256; TV: the tile, kVTile in the product
-template <int TV>
+// grid = B, block = 256; TV: the tile, kVTile in the product; kMetric: scat_mano_fit_verts_metric
+template <int TV, bool kMetric>
 __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
     __shared__ JacLds m;
     __shared__ VFitLds f;
@@ -456,12 +482,22 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
     const int tid = threadIdx.x, V = a.m.V;
     const float* tgt = a.targets + b * 3 * (int64_t)V;
     const float* wts = a.weights ? a.weights + b * (int64_t)V : nullptr;
+    const float* nrm = nullptr;
+    float tau = 1.f, ma = 1.f;
+    if constexpr (kMetric) {
+        nrm = a.normals + b * 3 * (int64_t)V;
+        tau = a.w_tangent;
+        ma = sqrtf(tau);
+    }
     vj_ancestors(m, a.m.parents);
     if (tid < kFU) f.p[tid] = a.init ? 0.f : a.p[b * kFU + tid];
     int bad = 0;
     for (int i = tid; i < 3 * V; i += kFThreads) bad |= !fit_finite(tgt[i]);
     if (wts) {
         for (int i = tid; i < V; i += kFThreads) bad |= !(fit_finite(wts[i]) && wts[i] >= 0.f);
+    }
+    if constexpr (kMetric) {
+        for (int i = tid; i < 3 * V; i += kFThreads) bad |= !fit_finite(nrm[i]);
     }
     if (tid == 0) {
         f.acc = 0;
@@ -480,7 +516,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
         vj_setup(m, pc, 0, false);   // the zero pose
         vfit_procrustes(m.s, pc, tgt, wts, reinterpret_cast<double*>(&tile[0][0]), f.p);
     }
-    vfit_cost(m, f, pc, f.p, tgt, wts, a.w_pose, a.w_beta);
+    vfit_cost<kMetric>(m, f, pc, f.p, tgt, wts, a.w_pose, a.w_beta, nrm, tau);
     if (tid == 0) f.cost = f.ct;
     const uint64_t fm = a.free_mask;
     int bi0 = 0;   // this thread's block of [J r]^T [J r]: rows 3 bi0.., columns 3 bj0.., bj0 <= bi0
@@ -520,6 +556,16 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
                         for (int cc = 0; cc < 3; ++cc) row[c * kVCols + kFModel + cc] = cc == c ? sw : 0.f;
                         row[c * kVCols + kFU - 1] = sw * sx;
                         row[c * kVCols + kFU] = wv != 0.f ? sw * ((sx + tr[c]) - tgt[3 * v + c]) : 0.f;
+                    }
+                }
+                if constexpr (kMetric) {   // the columns this work-item wrote, through sqrt(M_v)
+                    const float n[3] = {nrm[3 * v], nrm[3 * v + 1], nrm[3 * v + 2]};
+                    const float av = (n[0] == 0.f && n[1] == 0.f && n[2] == 0.f) ? 1.f : ma;
+                    if (k == 0) {
+                        for (int q = 0; q < 3; ++q) vfit_sqrt_metric(row + q, kVCols, n, av);
+                        for (int q = 3 + kFPose; q < kVCols; ++q) vfit_sqrt_metric(row + q, kVCols, n, av);
+                    } else {
+                        for (int q = 3 * k; q < 3 * k + 3; ++q) vfit_sqrt_metric(row + q, kVCols, n, av);
                     }
                 }
             }
@@ -575,7 +621,7 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
         __syncthreads();
         lm_solve<kFU>(f);
         if (tid < kFU) f.pt[tid] = ((fm >> tid) & 1u) ? f.p[tid] + f.delta[tid] : f.p[tid];
-        vfit_cost(m, f, pt, f.pt, tgt, wts, a.w_pose, a.w_beta);
+        vfit_cost<kMetric>(m, f, pt, f.pt, tgt, wts, a.w_pose, a.w_beta, nrm, tau);
         if (tid == 0) lm_accept<kFU>(f, f.ct);
         lm_commit<kFU>(f);
     }
@@ -607,19 +653,19 @@ static int fit_verts_launch(const char* fn, const float* blend, const float* joi
                             float lambda0, float w_pose, float w_beta, uint64_t free_mask, int tile, void* stream) {
     const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, targets, p, cost, accepted};
     VFitArgs a = {fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips),
-                  targets, weights, p, cost, accepted, iters, init, lambda0, w_pose, w_beta, free_mask};
+                  targets, weights, p, cost, accepted, iters, init, lambda0, w_pose, w_beta, free_mask, nullptr, 1.f};
     int rc = mano_validate(fn, ptrs, 9, B, V, parents, kNoTips, &a.m.levels);
     if (rc != SCAT_OK) return rc;
     rc = fit_check_args(fn, "Procrustes over the vertices", weights, iters, init, lambda0, w_pose, w_beta, free_mask);
     if (rc != SCAT_OK) return rc;
     const dim3 grid(B), block(kFThreads);
     if (tile == kVTile) {
-        hipLaunchKernelGGL(mano_fit_verts_kernel<kVTile>, grid, block, 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((mano_fit_verts_kernel<kVTile, false>), grid, block, 0, (hipStream_t)stream, a);
         set_kernel_label("mano_fit_verts_v%d_i%d", V, iters);
 #ifdef SCAT_DIAG
     } else if (tile == 8 || tile == 16) {
-        if (tile == 8) hipLaunchKernelGGL(mano_fit_verts_kernel<8>, grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(mano_fit_verts_kernel<16>, grid, block, 0, (hipStream_t)stream, a);
+        if (tile == 8) hipLaunchKernelGGL((mano_fit_verts_kernel<8, false>), grid, block, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((mano_fit_verts_kernel<16, false>), grid, block, 0, (hipStream_t)stream, a);
         set_kernel_label("mano_fit_verts_v%d_i%d_t%d", V, iters, tile);
 #endif
     } else {
@@ -635,6 +681,26 @@ extern "C" int scat_mano_fit_verts(const float* blend, const float* joint_t, con
                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
     return fit_verts_launch("scat_mano_fit_verts", blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, p, cost,
                             accepted, B, V, parents, iters, init, lambda0, w_pose, w_beta, free_mask, kVTile, stream);
+}
+
+extern "C" int scat_mano_fit_verts_metric(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                          const float* hands_mean, const float* targets, const float* weights,
+                                          const float* normals, float* p, float* cost, int* accepted, int B, int V,
+                                          uint64_t parents, int iters, float w_tangent, float lambda0, float w_pose,
+                                          float w_beta, uint64_t free_mask, void* stream) {
+    const char* fn = "scat_mano_fit_verts_metric";
+    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, targets, normals, p, cost, accepted};
+    VFitArgs a = {fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips),
+                  targets, weights, p, cost, accepted, iters, 0, lambda0, w_pose, w_beta, free_mask, normals, w_tangent};
+    int rc = mano_validate(fn, ptrs, 10, B, V, parents, kNoTips, &a.m.levels);
+    if (rc != SCAT_OK) return rc;
+    rc = fit_check_args(fn, "none: the start is the caller's", weights, iters, 0, lambda0, w_pose, w_beta, free_mask);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(w_tangent >= 0.f && w_tangent <= 1.f, SCAT_E_ARG, "%s: w_tangent %g outside 0..1", fn, (double)w_tangent);
+    hipLaunchKernelGGL((mano_fit_verts_kernel<kVTile, true>), dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
+    SCAT_LAUNCH_CHECK(fn);
+    set_kernel_label("mano_fit_verts_metric_v%d_i%d", V, iters);
+    return SCAT_OK;
 }
 
 #ifdef SCAT_DIAG

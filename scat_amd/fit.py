@@ -39,6 +39,13 @@ scanner's: nearest-vertex ICP from the caller's start, every round one assignmen
     res = fitter.fit_points(cloud, init=fitter.fit(joints), max_dist=0.03)     # PointFitResult; cloud [B,N,3]
     corr = fitter.nearest_vertices(res, cloud)         # Correspondences(idx, dist, vertex_weight, vertex_target, ...)
 
+fit_points_plane (include/scat_mano_fit_plane.h, the same two sources) is point-to-plane ICP for a cloud of points on the
+surface, which never hits the vertices: the residual counts along the matched vertex's normal and little across it.  It
+needs the model's faces (an array, or the MeshRenderer that draws the hand):
+
+    res = fitter.fit_points_plane(cloud, init=fitter.fit(joints), faces=renderer)      # PointFitResult, plane metric
+    normals = fitter.vertex_normals(res, renderer)     # [B,V,3]
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -46,6 +53,7 @@ import math
 import os
 from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from ._lib import HERE, ScatError, lib
@@ -61,8 +69,9 @@ SMOOTH_KEYS = ("rots", "poses", "betas", "trans", "scale")      # s_rots .. s_sc
 # s_rots .. s_ct of scat_mano_fit_seq_kp, in the entry point's order: the five, then the camera's scale and its offsets
 SMOOTH_KP_KEYS = SMOOTH_KEYS + ("cam_scale", "cam_trans")
 # bound on first use by lib().bind, beside _lib.py's tables: the MANO fits to a full mesh, a point cloud, a track of keypoints
-FIT_VERTS_HEADER, FIT_POINTS_HEADER, FIT_SEQ_KP_HEADER = (os.path.join(HERE, "..", "include", f"scat_mano_fit_{n}.h")
-                                                          for n in ("verts", "points", "seq_kp"))
+FIT_VERTS_HEADER, FIT_POINTS_HEADER, FIT_SEQ_KP_HEADER, FIT_PLANE_HEADER = (
+    os.path.join(HERE, "..", "include", f"scat_mano_fit_{n}.h") for n in ("verts", "points", "seq_kp", "plane"))
+MAX_F = 4096                   # SCAT_RENDER_MAX_F
 POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
 POINTS_MAX_ROUNDS = 64         # SCAT_FIT_POINTS_MAX_ROUNDS
 POINTS_MAX_STEPS = 256         # SCAT_FIT_POINTS_MAX_STEPS: rounds * iters
@@ -326,6 +335,75 @@ def mano_fit_points(model, points, weights, p, rounds, iters, max_dist, lambda0,
     return cost, accepted, idx, dist, ws[:32 * B].view(torch.float64).reshape(B, 4).clone()
 
 
+class Topology(NamedTuple):
+    """a mesh topology on the device, as scat_render.h and scat_mano_fit_plane.h take it"""
+    faces: torch.Tensor      # [F,3] int32
+    vf_off: torch.Tensor     # [V+1] int32
+    vf_idx: torch.Tensor     # [3F] int32: vf_idx[vf_off[v]:vf_off[v+1]] are the faces that name vertex v
+
+    @property
+    def F(self):
+        return int(self.faces.shape[0])
+
+    @property
+    def ptrs(self):
+        return _p(self.faces), _p(self.vf_off), _p(self.vf_idx)
+
+
+def mesh_normals(verts, topo):
+    """scat_mesh_normals as it is declared: verts [B,V,3], topo a Topology -> normals [B,V,3]"""
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    normals = torch.empty((B, V, 3), dtype=torch.float32, device=verts.device)
+    lib().bind(FIT_PLANE_HEADER).scat_mesh_normals(_p(verts), *topo.ptrs, _p(normals), B, V, topo.F, _stream())
+    return normals
+
+
+def mano_fit_verts_metric(model, targets, weights, normals, p, iters, w_tangent, lambda0, w_pose, w_beta, free=ALL_FREE):
+    """scat_mano_fit_verts_metric as it is declared: targets [B,V,3], weights [B,V] or None, normals [B,V,3], p [B,62] read
+    and written -> (cost [B], accepted [B] int32)"""
+    B = targets.shape[0]
+    cost, accepted = _results(B, targets.device)
+    lib().bind(FIT_PLANE_HEADER).scat_mano_fit_verts_metric(*_model_args(model), _p(targets), _p(weights), _p(normals), _p(p), _p(cost),
+                                                            _p(accepted), B, model.V, model.parents_packed, int(iters),
+                                                            float(w_tangent), float(lambda0), float(w_pose), float(w_beta),
+                                                            int(free), _stream())
+    return cost, accepted
+
+
+def mano_cloud_assign_plane(model, p, points, weights, topo, max_dist, w_tangent, want_model_pts=False):
+    """scat_mano_cloud_assign_plane as it is declared: p [B,62], points [B,N,3], weights [B,N] or None, topo a Topology ->
+    (Correspondences with the metric data cost, normals [B,V,3]), and with want_model_pts also model_pts [B,V,3]"""
+    B, V, N = p.shape[0], model.V, points.shape[1]
+    idx, dist, vw, vtarget, stats = _cloud_outputs(B, N, V, points.device)
+    normals = torch.empty((B, V, 3), dtype=torch.float32, device=points.device)
+    mp = torch.empty((B, V, 3), dtype=torch.float32, device=points.device) if want_model_pts else None
+    lib().bind(FIT_PLANE_HEADER).scat_mano_cloud_assign_plane(*_model_args(model), _p(p), _p(points), _p(weights), *topo.ptrs,
+                                                              float(max_dist), float(w_tangent), _p(mp), _p(normals), _p(idx), _p(dist),
+                                                              _p(vw), _p(vtarget), _p(stats), B, N, V, topo.F, model.parents_packed,
+                                                              _stream())
+    c = _correspondences(idx, dist, vw, vtarget, stats)
+    return (c, normals, mp) if want_model_pts else (c, normals)
+
+
+def mano_fit_points_plane(model, points, weights, topo, p, rounds, iters, max_dist, w_tangent, lambda0, w_pose, w_beta,
+                          free=ALL_FREE):
+    """scat_mano_fit_points_plane as it is declared: mano_fit_points with a Topology and w_tangent -> (data_cost [B] in the
+    plane metric, accepted [B] int32, idx [B,N] int32, dist [B,N], stats [B,4] fp64 of the last assignment).  The workspace
+    is allocated here, at the size scat_mano_fit_points_plane_ws gives (0 for sizes the launch refuses)."""
+    B, N = int(points.shape[0]), int(points.shape[1])
+    dev = points.device
+    cost, accepted = _results(B, dev)
+    idx = torch.empty((B, N), dtype=torch.int32, device=dev)
+    dist = torch.empty((B, N), dtype=torch.float32, device=dev)
+    ns = lib().bind(FIT_PLANE_HEADER)
+    ws, nbytes = _workspace(ns.scat_mano_fit_points_plane_ws, (B, N, model.V, topo.F), dev, max(32 * B, 16))
+    ns.scat_mano_fit_points_plane(*_model_args(model), _p(points), _p(weights), *topo.ptrs, _p(p), _p(cost), _p(accepted), _p(idx),
+                                  _p(dist), _p(ws), nbytes, B, N, model.V, topo.F, model.parents_packed, int(rounds), int(iters),
+                                  float(max_dist), float(w_tangent), float(lambda0), float(w_pose), float(w_beta), int(free),
+                                  _stream())
+    return cost, accepted, idx, dist, ws[:32 * B].view(torch.float64).reshape(B, 4).clone()
+
+
 def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
                 w_beta, w_limit, sigma3, sigma2, half_w, half_h, free=ALL_FREE, free_cam=7):
     """scat_mano_fit_kp as it is declared: targets3 [B,21,3] / weights3 [B,21], targets2 [B,21,2] / weights2 [B,21] (None
@@ -506,6 +584,103 @@ class ManoFitter:
             raise ScatError(f"{what} needs a fit result or fp32 p [{B},{UNKNOWNS}], or fp32 verts [{B},V,3]")
         _need_gpu(what, p)
         return mano_cloud_assign(self.model, p.contiguous(), points, weights, d)
+
+    def _topology(self, what, faces, device):
+        """the Topology on `device` of faces: a MeshRenderer of the model's V (its uploaded arrays), or a [F,3] integer
+        array or tensor (the table from render.vertex_face_csr, uploaded once per object and cached by it)"""
+        from .render import MeshRenderer
+
+        if isinstance(faces, MeshRenderer):
+            self._host_topology(what, faces)
+            if faces.device != device:
+                faces.to(device)
+            return Topology(faces.faces_d, faces.vf_off_d, faces.vf_idx_d)
+        entry = self._host_topology(what, faces)
+        if str(device) not in entry[2]:
+            entry[2][str(device)] = Topology(*(torch.from_numpy(a).to(device) for a in entry[1]))
+        return entry[2][str(device)]
+
+    def _host_topology(self, what, faces):
+        """the host half of _topology, before any tensor is looked at: the checks, and for an array the CSR table, cached
+        by the object -> [faces, (f, vf_off, vf_idx) int32, {device: Topology}]; None for a MeshRenderer, which has its own"""
+        from .render import MeshRenderer, _int_array, vertex_face_csr
+
+        V = self.model.V
+        if isinstance(faces, MeshRenderer):
+            if faces.V != V:
+                raise ScatError(f"{what}: the renderer has {faces.V} vertices, the model {V}")
+            return None
+        cache = self.__dict__.setdefault("_topologies", {})
+        hit = cache.get(id(faces))
+        if hit is not None and hit[0] is faces:
+            return hit
+        try:
+            f = _int_array(f"{what}: faces", faces, (3,))
+        except ValueError as e:
+            raise ScatError(str(e)) from None
+        if not 1 <= f.shape[0] <= MAX_F:
+            raise ScatError(f"{what}: {f.shape[0]} faces outside 1..{MAX_F}")
+        if f.min() < 0 or f.max() >= V:
+            raise ScatError(f"{what}: face indices {f.min()}..{f.max()} outside 0..{V - 1}")
+        off, idx = vertex_face_csr(f, V)
+        if len(cache) >= 8:      # a caller that makes a new array per call is not to grow the fitter
+            cache.pop(next(iter(cache)))
+        # the object is kept, so its id stays its own
+        cache[id(faces)] = [faces, tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (f, off, idx)), {}]
+        return cache[id(faces)]
+
+    def fit_points_plane(self, points, init, faces, weights=None, rounds=10, iters=4, max_dist=None, w_tangent=0.01, free=ALL_FREE):
+        """points [B,N,3] fp32, a cloud of points ON THE SURFACE (a depth camera's, a scanner's) with N <= 8192 ->
+        PointFitResult.  Point-to-plane ICP: fit_points' loop, where the residual of a point counts fully along the normal
+        of the model vertex it is matched to and with the weight w_tangent across it, so that points between the model's
+        vertices can slide on the surface instead of pulling the vertices under them.  faces: the model's topology, a
+        [F,3] integer array or tensor (F <= 4096, indices below V; uploaded once per object and cached by it: do not
+        modify it in place) or a MeshRenderer of the model's V.  w_tangent in [0, 1]: 1 is fit_points' cost, 0 the pure
+        point-to-plane cost, which leaves a sparse cloud's system rank-deficient; the default suits a dense cloud.
+        The result's data_cost and rms are IN THE PLANE METRIC, sum w (w_tangent |r|^2 + (1 - w_tangent) (n . r)^2) over the
+        matched points and sqrt(data_cost / matched weight): not comparable with fit_points' figures.  idx and dist are
+        Euclidean, to the nearest vertex.  init, weights, rounds, iters, max_dist, free, the limits and what makes a hand
+        unusable are fit_points'.  On a cloud that IS the model's vertices fit_points is the better method."""
+        what = "ManoFitter.fit_points_plane"
+        if init is None:
+            raise ScatError(f"{what} needs a start: p [B,62] or a fit result")
+        tau = float(w_tangent)
+        if not 0.0 <= tau <= 1.0:
+            raise ScatError(f"{what}: w_tangent {w_tangent} outside 0..1")
+        self._host_topology(what, faces)
+        points, weights = self._cloud(what, points, weights)
+        B = points.shape[0]
+        topo = self._topology(what, faces, points.device)
+        if isinstance(init, KeypointFitResult):
+            init = init.p[:, :UNKNOWNS]
+        p = _start(what, init, (FitResult, PointFitResult), (B, UNKNOWNS), points.device)
+        rounds, iters = int(rounds), int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
+            raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
+                            f"{POINTS_MAX_STEPS} steps")
+        cost, accepted, idx, dist, stats = mano_fit_points_plane(self.model, points, weights, topo, p, rounds, iters,
+                                                                 _max_dist(what, max_dist), tau, self.lambda0, self.w_pose,
+                                                                 self.w_beta, free)
+        mw = stats[:, 1]
+        rms = torch.where(mw > 0, (stats[:, 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
+        return PointFitResult(*_groups(p), cost, accepted, p, stats[:, 2].long(), rms, idx, dist)
+
+    def vertex_normals(self, result_or_verts, faces):
+        """-> [B,V,3] fp32, the area-weighted unit vertex normals of the fitted mesh of a result (mesh(result)) or of the
+        caller's vertices [B,V,3], for the topology `faces` (as in fit_points_plane): fp64 sums rounded to fp32 once, a
+        zero vector for a vertex in no face or of zero area"""
+        what = "ManoFitter.vertex_normals"
+        self._host_topology(what, faces)
+        verts =result_or_verts if isinstance(result_or_verts, torch.Tensor) and result_or_verts.dim() == 3 else None
+        if verts is None:
+            if not hasattr(result_or_verts, "p") or result_or_verts.p.dim() != 2:
+                raise ScatError(f"{what} needs a fit result of a batch or fp32 verts [B,{self.model.V},3]")
+            verts = self.mesh(result_or_verts)
+        _need_gpu(what, verts)
+        if verts.shape[0] == 0 or tuple(verts.shape[1:]) != (self.model.V, 3) or verts.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 verts [B,{self.model.V},3] with B >= 1, got {verts.dtype} {tuple(verts.shape)}")
+        return mesh_normals(verts.contiguous(), self._topology(what, faces, verts.device))
 
     def fit_mesh_outputs(self, out, weights=None):
         """out [B,21+V,3]: joints and mesh in the layout of ManoLayer / scat_mano_fwd; the V vertex rows are fitted"""
