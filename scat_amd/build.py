@@ -27,7 +27,7 @@ def _sources():
 # include/ instead, so a header added later counts before anyone names it here.
 PUBLIC_HEADERS = ("scat_hip.h", "scat_mesh_eval.h", "scat_eval.h", "scat_render.h", "scat_mano.h", "scat_mano_fit.h",
                   "scat_mano_fit_kp.h", "scat_mano_fit_seq.h", "scat_mano_fit_verts.h", "scat_mano_fit_points.h",
-                  "scat_mano_fit_seq_kp.h", "scat_mano_fit_plane.h")
+                  "scat_mano_fit_seq_kp.h", "scat_mano_fit_plane.h", "scat_mano_fit_seq_verts.h")
 INCLUDE = os.path.join(HERE, "..", "include")
 
 

@@ -23,10 +23,12 @@
 // registers, writes it to the caller, and adds rho instead of d2 to the data cost; W, S, the walk and the index array do
 // not know, so every other output keeps the bits of the plain form.  No LDS is added.  mesh_normals_kernel is the same
 // function on the caller's vertices.  scat_mano_fit_points_plane is the loop with scat_mano_fit_verts_metric.
-#include "mano_fit_common.h"
+#include "mano_fit_seq_common.h"
 
 #include "../../include/scat_mano_fit_plane.h"
 #include "../../include/scat_mano_fit_points.h"
+#include "../../include/scat_mano_fit_seq_verts.h"
+#include "mano_fit_seq_verts.h"
 
 namespace scat {
 
@@ -608,3 +610,88 @@ extern "C" int scat_mesh_normals(const float* verts, const int32_t* faces, const
     return SCAT_OK;
 }
 
+
+// ICP over a track of clouds, include/scat_mano_fit_seq_verts.h: points_loop's rounds with the S T frames as the
+// assignment's batch and mano_fit_seq_verts.hip's track solve in place of the per-hand fit.  The assignment's stats go to
+// the solve, which bridges a frame where nothing matched and refuses the sequence of an unusable one; the accepted counts
+// add up in the track kernel, so the assignment folds nothing (fold = 0).
+extern "C" int64_t scat_mano_fit_points_seq_ws(int S, int T, int N, int V, int F) {
+    if (S < 1 || T < 1 || T > SCAT_FIT_SEQ_MAX_T || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV || F < 0 || F > SCAT_RENDER_MAX_F)
+        return 0;
+    const int64_t B = (int64_t)S * T;
+    if (B > INT32_MAX) return 0;   // S T is the assignment's batch and a grid size
+    return (F ? plane_ws_total(B, N, V) : points_ws(B, N, V).total) + seq_verts_ws_bytes(S, T, V);
+}
+
+extern "C" int scat_mano_fit_points_seq(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                        const float* hands_mean, const float* points, const float* weights, const int32_t* faces,
+                                        const int32_t* vf_off, const int32_t* vf_idx, float* p, float* data_cost, int* accepted,
+                                        int* idx, float* dist, void* ws, int64_t ws_bytes, int S, int T, int N, int V, int F,
+                                        uint64_t parents, int rounds, int iters, float max_dist, float w_tangent, float lambda0,
+                                        float w_pose, float w_beta, float s_rots, float s_poses, float s_betas, float s_trans,
+                                        float s_scale, uint64_t free_mask, void* stream) {
+    const char* fn = "scat_mano_fit_points_seq";
+    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, points, p, data_cost, accepted};
+    CloudArgs a = {};
+    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
+    int rc = mano_validate(fn, ptrs, 9, S, V, parents, kNoTips, &a.m.levels);
+    if (rc != SCAT_OK) return rc;
+    rc = seq_check_frames(fn, T);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE((int64_t)S * T <= INT32_MAX, SCAT_E_SHAPE, "%s: %d sequences of %d frames are more than %d frames in all", fn, S, T,
+                 INT32_MAX);
+    const void* nullable[] = {weights, idx, dist};
+    rc = cloud_check(fn, nullable, 3, nullptr, N, max_dist);
+    if (rc != SCAT_OK) return rc;
+    const bool plane = faces || vf_off || vf_idx || F != 0;
+    if (plane) {
+        rc = topo_check(fn, faces, vf_off, vf_idx, F);
+        if (rc == SCAT_OK) rc = tau_check(fn, w_tangent);
+        if (rc != SCAT_OK) return rc;
+    }
+    SCAT_REQUIRE(rounds >= 1 && rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, rounds,
+                 SCAT_FIT_POINTS_MAX_ROUNDS);
+    rc = fit_check_solver(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(rounds * iters <= SCAT_FIT_POINTS_MAX_STEPS, SCAT_E_ARG, "%s: %d rounds of %d iterations are more than %d steps",
+                 fn, rounds, iters, SCAT_FIT_POINTS_MAX_STEPS);
+    const float sw[5] = {s_rots, s_poses, s_betas, s_trans, s_scale};
+    const char* const sn[5] = {"s_rots", "s_poses", "s_betas", "s_trans", "s_scale"};
+    rc = seq_check_smooth(fn, sw, sn, 5);
+    if (rc != SCAT_OK) return rc;
+    rc = fit_check_mask(fn, free_mask);
+    if (rc != SCAT_OK) return rc;
+    rc = seq_check_ws(fn, ws, ws_bytes, scat_mano_fit_points_seq_ws(S, T, N, V, F));
+    if (rc != SCAT_OK) return rc;
+
+    const int B = S * T;
+    const PointsWs w = points_ws(B, N, V);
+    const int64_t cloud_bytes = plane ? plane_ws_total(B, N, V) : w.total;
+    char* base = static_cast<char*>(ws);
+    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist;
+    a.idx = idx ? idx : reinterpret_cast<int*>(base + w.idx);
+    a.dist = dist ? dist : reinterpret_cast<float*>(base + w.dist);
+    a.vw = reinterpret_cast<float*>(base + w.vw), a.vtarget = reinterpret_cast<float*>(base + w.vtarget);
+    a.stats = reinterpret_cast<double*>(base + w.stats);
+    a.fold = 0, a.N = N, a.V = V;
+    if (plane) {
+        a.faces = faces, a.vf_off = vf_off, a.vf_idx = vf_idx, a.F = F, a.w_tangent = w_tangent;
+        a.normals = reinterpret_cast<float*>(base + w.total);
+    }
+    SeqVertsCall c = {blend, joint_t, joint_s, weights_t, hands_mean, a.vtarget, a.vw, plane ? a.normals : nullptr, a.stats, p,
+                      reinterpret_cast<float*>(base + w.cost), accepted, base + cloud_bytes, ws_bytes - cloud_bytes, S, T, V,
+                      parents, iters, 0, w_tangent, lambda0, w_pose, w_beta, {s_rots, s_poses, s_betas, s_trans, s_scale},
+                      free_mask, 0, stream};
+    for (int r = 0; r <= rounds; ++r) {
+        a.data_cost = r == rounds ? data_cost : nullptr;
+        rc = plane ? cloud_launch<true, true>(fn, a, B, stream) : cloud_launch<true>(fn, a, B, stream);
+        if (rc != SCAT_OK) return rc;
+        if (r == rounds) break;
+        c.acc_add = r > 0;
+        rc = seq_verts_solve(fn, nullptr, c);
+        if (rc != SCAT_OK) return rc;
+    }
+    set_kernel_label(plane ? "mano_fit_points_seq_plane_v%d_n%d_t%d_r%d_i%d" : "mano_fit_points_seq_v%d_n%d_t%d_r%d_i%d", V, N, T,
+                     rounds, iters);
+    return SCAT_OK;
+}

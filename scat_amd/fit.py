@@ -46,6 +46,14 @@ needs the model's faces (an array, or the MeshRenderer that draws the hand):
     res = fitter.fit_points_plane(cloud, init=fitter.fit(joints), faces=renderer)      # PointFitResult, plane metric
     normals = fitter.vertex_normals(res, renderer)     # [B,V,3]
 
+fit_vertices_sequence and fit_points_sequence (include/scat_mano_fit_seq_verts.h, csrc/mano_fit_seq_verts.hip) are the
+last two over a track, what a depth camera's clip needs: the frames are assembled side by side, one workgroup each, and
+one workgroup per track eliminates along the frames; a frame in which nothing matches is bridged by its neighbours:
+
+    res = fitter.fit_vertices_sequence(meshes, smooth=dict(rots=4e-3, poses=4e-3, trans=4.0))   # meshes [S,T,V,3]
+    res = fitter.fit_points_sequence(clouds, init=fitter.fit_sequence(joints), faces=renderer, max_dist=0.03)
+    frames = renderer.render(fitter.mesh(res).flatten(0, 1), cams)
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -71,6 +79,8 @@ SMOOTH_KP_KEYS = SMOOTH_KEYS + ("cam_scale", "cam_trans")
 # bound on first use by lib().bind, beside _lib.py's tables: the MANO fits to a full mesh, a point cloud, a track of keypoints
 FIT_VERTS_HEADER, FIT_POINTS_HEADER, FIT_SEQ_KP_HEADER, FIT_PLANE_HEADER = (
     os.path.join(HERE, "..", "include", f"scat_mano_fit_{n}.h") for n in ("verts", "points", "seq_kp", "plane"))
+# the MANO fit to a track of meshes and to a track of point clouds
+FIT_SEQ_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_seq_verts.h")
 MAX_F = 4096                   # SCAT_RENDER_MAX_F
 POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
 POINTS_MAX_ROUNDS = 64         # SCAT_FIT_POINTS_MAX_ROUNDS
@@ -157,6 +167,21 @@ class PointFitResult(NamedTuple):
     rms: torch.Tensor        # [B]: sqrt(data_cost / matched weight), +inf when nothing matched
     idx: torch.Tensor        # [B,N] int32: the nearest vertex at p, -1 for a point of weight 0
     dist: torch.Tensor       # [B,N]
+
+
+class PointSequenceFitResult(NamedTuple):
+    rots: torch.Tensor       # [S,T,3]
+    poses: torch.Tensor      # [S,T,45]
+    betas: torch.Tensor      # [S,T,10]
+    trans: torch.Tensor      # [S,T,3]
+    scale: torch.Tensor      # [S,T]
+    data_cost: torch.Tensor  # [S,T]: sum w d^2 (with faces: the plane metric) over a frame's matched points at p; +inf: unusable
+    accepted: torch.Tensor   # [S] int32: accepted steps of the sequence, summed over the rounds
+    p: torch.Tensor          # [S,T,62]: the five groups as the kernel holds them (log_scale last)
+    matched: torch.Tensor    # [S,T] int64: matched points at p
+    rms: torch.Tensor        # [S,T]: sqrt(data_cost / matched weight), +inf when nothing matched
+    idx: torch.Tensor        # [S,T,N] int32: the nearest vertex at p, -1 for a point of weight 0
+    dist: torch.Tensor       # [S,T,N]
 
 
 def _check_model(what, model, ref):
@@ -432,6 +457,44 @@ def mano_fit_seq(model, targets, weights, joint_map, p, iters, init, lambda0, w_
                         float(w_beta), float(s_rots), float(s_poses), float(s_betas), float(s_trans), float(s_scale), int(free),
                         _stream())
     return cost, accepted
+
+
+def mano_fit_seq_verts(model, targets, weights, normals, p, iters, init, w_tangent, lambda0, w_pose, w_beta, smooth5,
+                       free=ALL_FREE):
+    """scat_mano_fit_seq_verts as it is declared: targets [S,T,V,3], weights [S,T,V] or None, normals [S,T,V,3] or None
+    (which selects the plane metric with w_tangent), p [S,T,62] (read when init = 0, written), smooth5 = (s_rots, s_poses,
+    s_betas, s_trans, s_scale) -> (cost [S], accepted [S] int32).  The workspace is allocated here, at the size
+    scat_mano_fit_seq_verts_ws gives (0 for sizes the launch refuses)."""
+    S, T = int(targets.shape[0]), int(targets.shape[1])
+    cost, accepted = _results(S, targets.device)
+    ns = lib().bind(FIT_SEQ_VERTS_HEADER)
+    ws, nbytes = _workspace(ns.scat_mano_fit_seq_verts_ws, (S, T, model.V), targets.device)
+    ns.scat_mano_fit_seq_verts(*_model_args(model), _p(targets), _p(weights), _p(normals), _p(p), _p(cost), _p(accepted), _p(ws),
+                               nbytes, S, T, model.V, model.parents_packed, int(iters), int(init), float(w_tangent), float(lambda0),
+                               float(w_pose), float(w_beta), *(float(v) for v in smooth5), int(free), _stream())
+    return cost, accepted
+
+
+def mano_fit_points_seq(model, points, weights, topo, p, rounds, iters, max_dist, w_tangent, lambda0, w_pose, w_beta, smooth5,
+                        free=ALL_FREE):
+    """scat_mano_fit_points_seq as it is declared: points [S,T,N,3], weights [S,T,N] or None, topo a Topology or None
+    (nearest vertex), p [S,T,62] read and written -> (data_cost [S,T], accepted [S] int32, idx [S,T,N] int32, dist [S,T,N],
+    stats [S,T,4] fp64 of the last assignment).  The workspace is allocated here, at the size scat_mano_fit_points_seq_ws
+    gives (0 for sizes the launch refuses)."""
+    S, T, N = (int(n) for n in points.shape[:3])
+    dev = points.device
+    cost = torch.empty((S, T), dtype=torch.float32, device=dev)
+    accepted = torch.empty((S,), dtype=torch.int32, device=dev)
+    idx = torch.empty((S, T, N), dtype=torch.int32, device=dev)
+    dist = torch.empty((S, T, N), dtype=torch.float32, device=dev)
+    ns = lib().bind(FIT_SEQ_VERTS_HEADER)
+    F = 0 if topo is None else topo.F
+    ws, nbytes = _workspace(ns.scat_mano_fit_points_seq_ws, (S, T, N, model.V, F), dev, max(32 * S * T, 16))
+    ns.scat_mano_fit_points_seq(*_model_args(model), _p(points), _p(weights), *((0, 0, 0) if topo is None else topo.ptrs), _p(p),
+                                _p(cost), _p(accepted), _p(idx), _p(dist), _p(ws), nbytes, S, T, N, model.V, F,
+                                model.parents_packed, int(rounds), int(iters), float(max_dist), float(w_tangent), float(lambda0),
+                                float(w_pose), float(w_beta), *(float(v) for v in smooth5), int(free), _stream())
+    return cost, accepted, idx, dist, ws[:32 * S * T].view(torch.float64).reshape(S, T, 4).clone()
 
 
 def mano_fit_seq_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
@@ -713,12 +776,100 @@ class ManoFitter:
                             f"{tuple(joints.shape)}")
         S, T = int(joints.shape[0]), int(joints.shape[1])
         weights = _weights(what, weights, (S, T, 21))
-        p = _start(what, init, SequenceFitResult, (S, T, UNKNOWNS), joints.device)
+        p = _start(what, init, (SequenceFitResult, PointSequenceFitResult), (S, T, UNKNOWNS), joints.device)
         iters = self.iters if iters is None else int(iters)
         _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
         cost, accepted = mano_fit_seq(self.model, joints.contiguous(), weights, self._map_on(joints.device), p, iters,
                                       0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, *sm, free)
         return SequenceFitResult(*_groups(p), cost, accepted, p)
+
+    def _start_sequence(self, what, init, S, T, device):
+        """the p [S,T,62] of a mesh or cloud track: of a KeypointSequenceFitResult the first 62"""
+        if isinstance(init, KeypointSequenceFitResult):
+            init = init.p[..., :UNKNOWNS]
+        return _start(what, init, (SequenceFitResult, PointSequenceFitResult), (S, T, UNKNOWNS), device)
+
+    def fit_vertices_sequence(self, verts, weights=None, smooth=None, init=None, free=ALL_FREE, iters=None):
+        """verts [S,T,V,3] fp32, S tracks of T <= 256 meshes in the model's topology -> SequenceFitResult.  fit_vertices'
+        data term in every frame and fit_sequence's penalty sum_i d_i (p_t,i - p_t-1,i)^2 between consecutive frames, one
+        Levenberg-Marquardt per track: one lambda, one accept / reject.  The frames are assembled side by side, one
+        workgroup each, and only the elimination along the track runs one workgroup per sequence: 2 iters + 2 launches
+        (two more for the Procrustes start), no synchronisation with the host.
+        smooth: dict(rots=, poses=, betas=, trans=, scale=) as in fit_sequence.  UNITS: each weight multiplies a squared
+        difference in the unknown's own unit (radians squared for rots and poses, on the axis-angle numbers), and the data
+        term it is weighed against is in the vertices' unit squared SUMMED OVER V VERTICES: V / 21 times a joints track's
+        at the same residual, so weights that suit fit_sequence are about V / 21 times too small here.
+        weights: [S,T,V] or None (all ones).  A frame whose weights are all zero is legal whatever its finite vertices:
+        it has no data term and is bridged by its neighbours; this is also how a short clip is padded to T frames.
+        init: None for the Procrustes start over the vertices frame by frame (continuous in rots; a zero-weight frame takes
+        its neighbour's), or p [S,T,62] / a SequenceFitResult, KeypointSequenceFitResult (its first 62) or
+        PointSequenceFitResult (it is not modified): a joints track of the same hands is the natural warm start.
+        free: bit i clear freezes unknown i in every frame.  A sequence with a vertex or weight that is not finite, a
+        negative weight or a start that is not finite, in any frame, is not fitted: cost +inf, accepted 0, p its start
+        (zeros for the Procrustes start)."""
+        what = "ManoFitter.fit_vertices_sequence"
+        sm = _smooth(what, smooth)
+        _need_gpu(what, verts, *(() if weights is None else (weights,)))
+        _check_model(what, self.model, verts)
+        V = self.model.V
+        if verts.dim() != 4 or verts.shape[0] == 0 or not 1 <= verts.shape[1] <= SEQ_MAX_T or tuple(verts.shape[2:]) != (V, 3) \
+                or verts.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 verts [S,T,{V},3] with S >= 1 and T in 1..{SEQ_MAX_T}, got {verts.dtype} "
+                            f"{tuple(verts.shape)}")
+        S, T = int(verts.shape[0]), int(verts.shape[1])
+        weights = _weights(what, weights, (S, T, V))
+        p = self._start_sequence(what, init, S, T, verts.device)
+        iters = self.iters if iters is None else int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        cost, accepted = mano_fit_seq_verts(self.model, verts.contiguous(), weights, None, p, iters, 0 if init is not None else 1,
+                                            1.0, self.lambda0, self.w_pose, self.w_beta, sm, free)
+        return SequenceFitResult(*_groups(p), cost, accepted, p)
+
+    def fit_points_sequence(self, points, init, faces=None, weights=None, smooth=None, rounds=None, iters=4, max_dist=None,
+                            w_tangent=0.01, free=ALL_FREE):
+        """points [S,T,N,3] fp32, S tracks of T <= 256 unordered clouds with N <= 8192 (a depth camera's clip) ->
+        PointSequenceFitResult.  ICP over the track: `rounds` times {every point of every frame to its nearest model
+        vertex, one launch over the S T frames; `iters` iterations of fit_vertices_sequence's solve on the per-vertex
+        centroids}, then one more assignment that the result's idx, dist, matched, data_cost and rms describe.
+        faces: the model's topology (an array or a MeshRenderer, as in fit_points_plane) selects point-to-plane ICP with
+        w_tangent, for points ON THE SURFACE; None is nearest-vertex ICP (fit_points).  rounds: None is 10 with faces
+        and 5 without.  init: the start, required, p [S,T,62] or a sequence result (it is not modified): a joints track
+        is the natural start.  smooth: as in fit_vertices_sequence; the data term is summed over the matched points.
+        A frame in which nothing is matched (an occluded hand: every point beyond max_dist or of weight 0) is BRIDGED by
+        its neighbours, as a zero-weight frame is; its matched is 0 and its rms +inf.  A sequence with a point, weight or
+        start that is not finite, or a negative weight, in any frame is not fitted: p its start, accepted 0, and
+        data_cost +inf in the frames concerned.  The other sequences are not affected.
+        weights, max_dist, free and the limits (rounds in 1..64, rounds x iters <= 256) are fit_points'."""
+        what = "ManoFitter.fit_points_sequence"
+        if init is None:
+            raise ScatError(f"{what} needs a start: p [S,T,62] or a sequence fit result")
+        sm = _smooth(what, smooth)
+        tau = float(w_tangent)
+        if not 0.0 <= tau <= 1.0:
+            raise ScatError(f"{what}: w_tangent {w_tangent} outside 0..1")
+        if faces is not None:
+            self._host_topology(what, faces)
+        _need_gpu(what, points, *(() if weights is None else (weights,)))
+        _check_model(what, self.model, points)
+        if points.dim() != 4 or points.shape[0] == 0 or not 1 <= points.shape[1] <= SEQ_MAX_T \
+                or not 1 <= points.shape[2] <= POINTS_MAX_N or points.shape[3] != 3 or points.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 points [S,T,N,3] with S >= 1, T in 1..{SEQ_MAX_T} and N in 1..{POINTS_MAX_N}, "
+                            f"got {points.dtype} {tuple(points.shape)}")
+        S, T = int(points.shape[0]), int(points.shape[1])
+        weights = _weights(what, weights, tuple(points.shape[:3]))
+        topo = None if faces is None else self._topology(what, faces, points.device)
+        p = self._start_sequence(what, init, S, T, points.device)
+        rounds, iters = int((10 if faces is not None else 5) if rounds is None else rounds), int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
+            raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
+                            f"{POINTS_MAX_STEPS} steps")
+        cost, accepted, idx, dist, stats = mano_fit_points_seq(self.model, points.contiguous(), weights, topo, p, rounds, iters,
+                                                               _max_dist(what, max_dist), tau, self.lambda0, self.w_pose,
+                                                               self.w_beta, sm, free)
+        mw = stats[..., 1]
+        rms = torch.where(mw > 0, (stats[..., 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
+        return PointSequenceFitResult(*_groups(p), cost, accepted, p, stats[..., 2].long(), rms, idx, dist)
 
     def fit_outputs_sequence(self, out66, weights=None, smooth=None):
         """out66 [S,T,66]: the network's camera and 21 root-relative joints for every frame of S tracks; the joints are
@@ -839,10 +990,10 @@ class ManoFitter:
     def _posed(self, r):
         _need_gpu("ManoFitter.mesh", r.p)
         _check_model("ManoFitter.mesh", self.model, r.p)
-        if isinstance(r, (SequenceFitResult, KeypointSequenceFitResult)):      # every frame as one batch, then back to [S,T,...]
+        if isinstance(r, (SequenceFitResult, KeypointSequenceFitResult, PointSequenceFitResult)):      # every frame as one batch, then back to [S,T,...]
             S, T = r.p.shape[:2]
             p = r.p[..., :UNKNOWNS].reshape(S * T, UNKNOWNS)
-            j, v = self._posed(FitResult(*_groups(p), r.cost, r.accepted, p))
+            j, v = self._posed(FitResult(*_groups(p), None, r.accepted, p))
             return j.reshape(S, T, 21, 3), v.reshape(S, T, -1, 3)
         out = mano_fwd(self.model, r.rots.contiguous(), r.poses.contiguous(), r.betas.contiguous())
         out = r.scale[:, None, None] * out + r.trans[:, None, :]
