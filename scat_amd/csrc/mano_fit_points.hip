@@ -15,20 +15,24 @@
 //                  wavefront, the four wavefronts ascending.
 // The usable-inputs scan of the points and their weights is mano_fit_common.h's fit_unusable.
 // Static LDS at the largest sizes: 18 KiB of vertices, 32 KiB of indices, 2.6 KiB of pose state: 53 KiB of the 64.
-// scat_mano_fit_points launches {assign, scat_mano_fit_verts} `rounds` times and one last assign; each assign after the
-// first adds the accepted count of the fit before it to the caller's total.
+// icp_loop is every loop of launches: the checks, the workspace (points_ws, which knows whether the normals and a track
+// solve's part follow), the CloudArgs (cloud_args, the assignment entry points' filler too) and `rounds` times {assign,
+// solve}, then one last assign.  The solve is passed in, checked once and launched unchecked every round: the mesh fit
+// (mano_fit_verts.h) for scat_mano_fit_points, where each assign after the first adds the accepted count of the fit
+// before it to the caller's total, and the track solve (mano_fit_seq_verts.h) for scat_mano_fit_points_seq.
 //
 // kPlane (include/scat_mano_fit_plane.h, point-to-plane ICP): the thread that owns vertex v in the reduction first forms
 // the vertex normal from the LDS model points and the topology in global memory (mesh_vertex_normal, fp64), keeps it in
 // registers, writes it to the caller, and adds rho instead of d2 to the data cost; W, S, the walk and the index array do
 // not know, so every other output keeps the bits of the plain form.  No LDS is added.  mesh_normals_kernel is the same
-// function on the caller's vertices.  scat_mano_fit_points_plane is the loop with scat_mano_fit_verts_metric.
+// function on the caller's vertices.  scat_mano_fit_points_plane is icp_loop with a topology and the metric mesh fit.
 #include "mano_fit_seq_common.h"
 
 #include "../../include/scat_mano_fit_plane.h"
 #include "../../include/scat_mano_fit_points.h"
 #include "../../include/scat_mano_fit_seq_verts.h"
 #include "mano_fit_seq_verts.h"
+#include "mano_fit_verts.h"
 
 namespace scat {
 
@@ -377,88 +381,6 @@ static int cloud_launch(const char* fn, const CloudArgs& a, int B, void* stream)
     return SCAT_OK;
 }
 
-extern "C" int scat_cloud_assign(const float* verts, const float* points, const float* weights, float max_dist, int* idx,
-                                 float* dist, float* vw, float* vtarget, double* stats, int B, int N, int V, void* stream) {
-    const char* fn = "scat_cloud_assign";
-    const void* ptrs[] = {verts, points, idx, dist, vw, vtarget, stats};
-    uintptr_t all = 0;
-    for (const void* q : ptrs) {
-        SCAT_REQUIRE(q, SCAT_E_ARG, "%s: null pointer", fn);
-        all |= (uintptr_t)q;
-    }
-    SCAT_REQUIRE((all & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
-    SCAT_REQUIRE(B > 0, SCAT_E_SHAPE, "%s: batch %d must be positive", fn, B);
-    SCAT_REQUIRE(V >= 1 && V <= kMMaxV, SCAT_E_SHAPE, "%s: %d vertices outside 1..%d", fn, V, kMMaxV);
-    const void* nullable[] = {weights};
-    int rc = cloud_check(fn, nullable, 1, stats, N, max_dist);
-    if (rc != SCAT_OK) return rc;
-    CloudArgs a = {};
-    a.verts = verts, a.points = points, a.weights = weights, a.max_dist = max_dist;
-    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
-    rc = cloud_launch<false>(fn, a, B, stream);
-    if (rc != SCAT_OK) return rc;
-    set_kernel_label("cloud_assign_v%d_n%d", V, N);
-    return SCAT_OK;
-}
-
-extern "C" int scat_mano_cloud_assign(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
-                                      const float* hands_mean, const float* p, const float* points, const float* weights,
-                                      float max_dist, float* model_pts, int* idx, float* dist, float* vw, float* vtarget,
-                                      double* stats, int B, int N, int V, uint64_t parents, void* stream) {
-    const char* fn = "scat_mano_cloud_assign";
-    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, p, points, idx, dist, vw, vtarget, stats};
-    CloudArgs a = {};
-    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
-    int rc = mano_validate(fn, ptrs, 12, B, V, parents, kNoTips, &a.m.levels);
-    if (rc != SCAT_OK) return rc;
-    const void* nullable[] = {weights, model_pts};
-    rc = cloud_check(fn, nullable, 2, stats, N, max_dist);
-    if (rc != SCAT_OK) return rc;
-    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist, a.model_pts = model_pts;
-    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
-    rc = cloud_launch<true>(fn, a, B, stream);
-    if (rc != SCAT_OK) return rc;
-    set_kernel_label("mano_cloud_assign_v%d_n%d", V, N);
-    return SCAT_OK;
-}
-
-// the workspace of scat_mano_fit_points: byte offsets, every part rounded up to 16 bytes
-struct PointsWs { int64_t stats, vtarget, vw, cost, acc, idx, dist, total; };
-
-static PointsWs points_ws(int64_t B, int64_t N, int64_t V) {
-    PointsWs w;
-    int64_t off = 0;
-    const auto take = [&off](int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 15) & ~(int64_t)15;
-        return o;
-    };
-    w.stats = take(B * 4 * (int64_t)sizeof(double));
-    w.vtarget = take(B * V * 3 * (int64_t)sizeof(float));
-    w.vw = take(B * V * (int64_t)sizeof(float));
-    w.cost = take(B * (int64_t)sizeof(float));
-    w.acc = take(B * (int64_t)sizeof(int));
-    w.idx = take(B * N * (int64_t)sizeof(int));
-    w.dist = take(B * N * (int64_t)sizeof(float));
-    w.total = off;
-    return w;
-}
-
-extern "C" int64_t scat_mano_fit_points_ws(int B, int N, int V) {
-    if (B < 1 || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV) return 0;
-    return points_ws(B, N, V).total;
-}
-
-// the plane loop's workspace: scat_mano_fit_points' parts, then the normals [B,V,3]
-static int64_t plane_ws_total(int64_t B, int64_t N, int64_t V) {
-    return points_ws(B, N, V).total + ((B * V * 3 * (int64_t)sizeof(float) + 15) & ~(int64_t)15);
-}
-
-extern "C" int64_t scat_mano_fit_points_plane_ws(int B, int N, int V, int F) {
-    if (B < 1 || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV || F < 1 || F > SCAT_RENDER_MAX_F) return 0;
-    return plane_ws_total(B, N, V);
-}
-
 // the topology of a plane entry point: the three arrays present and aligned, F in range, tau in 0..1
 struct CloudTopo {
     const int32_t* faces;
@@ -476,96 +398,70 @@ static int topo_check(const char* fn, const int32_t* faces, const int32_t* vf_of
     return SCAT_OK;
 }
 
-static int tau_check(const char* fn, float w_tangent) {
-    SCAT_REQUIRE(w_tangent >= 0.f && w_tangent <= 1.f, SCAT_E_ARG, "%s: w_tangent %g outside 0..1", fn, (double)w_tangent);
-    return SCAT_OK;
-}
-
-// Both ICP loops: the checks, then 2 rounds + 1 launches.  topo null: scat_mano_fit_points; otherwise the plane form,
-// whose workspace ends with the normals
-static int points_loop(const char* fn, const char* label, const CloudTopo* topo, const float* blend, const float* joint_t,
-                       const float* joint_s, const float* weights_t, const float* hands_mean, const float* points,
-                       const float* weights, float* p, float* data_cost, int* accepted, int* idx, float* dist, void* ws,
-                       int64_t ws_bytes, int B, int N, int V, uint64_t parents, int rounds, int iters, float max_dist,
-                       float lambda0, float w_pose, float w_beta, uint64_t free_mask, void* stream) {
-    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, points, p, data_cost, accepted};
+// The one filler of CloudArgs, for the three assignment entry points and the ICP loop.  m and p: the model's form, verts:
+// the other; topo and normals: kPlane, or both null.  The ICP loop sets the fold and data_cost itself
+static CloudArgs cloud_args(const ManoArgs& m, const float* p, const float* verts, const float* points, const float* weights,
+                            float max_dist, float* model_pts, int* idx, float* dist, float* vw, float* vtarget, double* stats, int N,
+                            int V, const CloudTopo* topo, float* normals) {
     CloudArgs a = {};
-    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
-    int rc = mano_validate(fn, ptrs, 9, B, V, parents, kNoTips, &a.m.levels);
-    if (rc != SCAT_OK) return rc;
-    const void* nullable[] = {weights, idx, dist};
-    rc = cloud_check(fn, nullable, 3, nullptr, N, max_dist);
-    if (rc != SCAT_OK) return rc;
-    if (topo) {
-        rc = topo_check(fn, topo->faces, topo->vf_off, topo->vf_idx, topo->F);
-        if (rc == SCAT_OK) rc = tau_check(fn, topo->w_tangent);
-        if (rc != SCAT_OK) return rc;
-    }
-    SCAT_REQUIRE(rounds >= 1 && rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, rounds,
-                 SCAT_FIT_POINTS_MAX_ROUNDS);
-    rc = fit_check_solver(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
-    if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(rounds * iters <= SCAT_FIT_POINTS_MAX_STEPS, SCAT_E_ARG, "%s: %d rounds of %d iterations are more than %d steps",
-                 fn, rounds, iters, SCAT_FIT_POINTS_MAX_STEPS);
-    rc = fit_check_mask(fn, free_mask);
-    if (rc != SCAT_OK) return rc;
-    const PointsWs w = points_ws(B, N, V);
-    const int64_t need = topo ? plane_ws_total(B, N, V) : w.total;
-    SCAT_REQUIRE(ws && ((uintptr_t)ws & 15) == 0, SCAT_E_WORKSPACE, "%s: the workspace must be a 16-byte-aligned pointer", fn);
-    SCAT_REQUIRE(ws_bytes >= need, SCAT_E_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
-                 (long long)need);
-    char* base = static_cast<char*>(ws);
-    float* vtarget = reinterpret_cast<float*>(base + w.vtarget);
-    float* vw = reinterpret_cast<float*>(base + w.vw);
-    float* cost_r = reinterpret_cast<float*>(base + w.cost);
-    int* acc_r = reinterpret_cast<int*>(base + w.acc);
-    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist;
-    a.idx = idx ? idx : reinterpret_cast<int*>(base + w.idx);
-    a.dist = dist ? dist : reinterpret_cast<float*>(base + w.dist);
-    a.vw = vw, a.vtarget = vtarget, a.stats = reinterpret_cast<double*>(base + w.stats);
-    a.acc_round = acc_r, a.acc_total = accepted, a.N = N, a.V = V;
+    a.m = m, a.p = p, a.verts = verts, a.points = points, a.weights = weights, a.max_dist = max_dist, a.model_pts = model_pts;
+    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
     if (topo) {
         a.faces = topo->faces, a.vf_off = topo->vf_off, a.vf_idx = topo->vf_idx, a.F = topo->F, a.w_tangent = topo->w_tangent;
-        a.normals = reinterpret_cast<float*>(base + w.total);
+        a.normals = normals;
     }
-    for (int r = 0; r <= rounds; ++r) {
-        a.fold = r == 0 ? 1 : 2;
-        a.data_cost = r == rounds ? data_cost : nullptr;
-        rc = topo ? cloud_launch<true, true>(fn, a, B, stream) : cloud_launch<true>(fn, a, B, stream);
-        if (rc != SCAT_OK) return rc;
-        if (r == rounds) break;
-        rc = topo ? scat_mano_fit_verts_metric(blend, joint_t, joint_s, weights_t, hands_mean, vtarget, vw, a.normals, p, cost_r,
-                                               acc_r, B, V, parents, iters, topo->w_tangent, lambda0, w_pose, w_beta, free_mask,
-                                               stream)
-                  : scat_mano_fit_verts(blend, joint_t, joint_s, weights_t, hands_mean, vtarget, vw, p, cost_r, acc_r, B, V, parents,
-                                        iters, 0, lambda0, w_pose, w_beta, free_mask, stream);
-        if (rc != SCAT_OK) return rc;
+    return a;
+}
+
+extern "C" int scat_cloud_assign(const float* verts, const float* points, const float* weights, float max_dist, int* idx,
+                                 float* dist, float* vw, float* vtarget, double* stats, int B, int N, int V, void* stream) {
+    const char* fn = "scat_cloud_assign";
+    const void* ptrs[] = {verts, points, idx, dist, vw, vtarget, stats};
+    uintptr_t all = 0;
+    for (const void* q : ptrs) {
+        SCAT_REQUIRE(q, SCAT_E_ARG, "%s: null pointer", fn);
+        all |= (uintptr_t)q;
     }
-    set_kernel_label(label, V, N, rounds, iters);
+    SCAT_REQUIRE((all & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
+    SCAT_REQUIRE(B > 0, SCAT_E_SHAPE, "%s: batch %d must be positive", fn, B);
+    SCAT_REQUIRE(V >= 1 && V <= kMMaxV, SCAT_E_SHAPE, "%s: %d vertices outside 1..%d", fn, V, kMMaxV);
+    const void* nullable[] = {weights};
+    int rc = cloud_check(fn, nullable, 1, stats, N, max_dist);
+    if (rc != SCAT_OK) return rc;
+    rc = cloud_launch<false>(fn, cloud_args({}, nullptr, verts, points, weights, max_dist, nullptr, idx, dist, vw, vtarget, stats, N, V,
+                                            nullptr, nullptr), B, stream);
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label("cloud_assign_v%d_n%d", V, N);
     return SCAT_OK;
 }
 
-extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
-                                    const float* hands_mean, const float* points, const float* weights, float* p,
-                                    float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
-                                    int N, int V, uint64_t parents, int rounds, int iters, float max_dist, float lambda0,
-                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
-    return points_loop("scat_mano_fit_points", "mano_fit_points_v%d_n%d_r%d_i%d", nullptr, blend, joint_t, joint_s, weights_t,
-                       hands_mean, points, weights, p, data_cost, accepted, idx, dist, ws, ws_bytes, B, N, V, parents, rounds,
-                       iters, max_dist, lambda0, w_pose, w_beta, free_mask, stream);
+// Both model forms of the assignment: the checks, then the launch.  topo null: scat_mano_cloud_assign
+static int mano_assign(const char* fn, const CloudTopo* topo, const float* blend, const float* joint_t, const float* joint_s,
+                       const float* weights_t, const float* hands_mean, const float* p, const float* points, const float* weights,
+                       float max_dist, float* model_pts, float* normals, int* idx, float* dist, float* vw, float* vtarget,
+                       double* stats, int B, int N, int V, uint64_t parents, void* stream) {
+    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, p, points, idx, dist, vw, vtarget, stats, normals};
+    ManoArgs m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
+    int rc = mano_validate(fn, ptrs, topo ? 13 : 12, B, V, parents, kNoTips, &m.levels);
+    if (rc != SCAT_OK) return rc;
+    const void* nullable[] = {weights, model_pts};
+    rc = cloud_check(fn, nullable, 2, stats, N, max_dist);
+    if (rc == SCAT_OK && topo) rc = topo_check(fn, topo->faces, topo->vf_off, topo->vf_idx, topo->F);
+    if (rc == SCAT_OK && topo) rc = fit_check_tau(fn, topo->w_tangent);
+    if (rc != SCAT_OK) return rc;
+    const CloudArgs a = cloud_args(m, p, nullptr, points, weights, max_dist, model_pts, idx, dist, vw, vtarget, stats, N, V, topo, normals);
+    return topo ? cloud_launch<true, true>(fn, a, B, stream) : cloud_launch<true>(fn, a, B, stream);
 }
 
-extern "C" int scat_mano_fit_points_plane(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
-                                          const float* hands_mean, const float* points, const float* weights,
-                                          const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, float* p,
-                                          float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
-                                          int N, int V, int F, uint64_t parents, int rounds, int iters, float max_dist,
-                                          float w_tangent, float lambda0, float w_pose, float w_beta, uint64_t free_mask,
-                                          void* stream) {
-    const CloudTopo topo = {faces, vf_off, vf_idx, F, w_tangent};
-    return points_loop("scat_mano_fit_points_plane", "mano_fit_points_plane_v%d_n%d_r%d_i%d", &topo, blend, joint_t, joint_s,
-                       weights_t, hands_mean, points, weights, p, data_cost, accepted, idx, dist, ws, ws_bytes, B, N, V, parents,
-                       rounds, iters, max_dist, lambda0, w_pose, w_beta, free_mask, stream);
+extern "C" int scat_mano_cloud_assign(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                      const float* hands_mean, const float* p, const float* points, const float* weights,
+                                      float max_dist, float* model_pts, int* idx, float* dist, float* vw, float* vtarget,
+                                      double* stats, int B, int N, int V, uint64_t parents, void* stream) {
+    const int rc = mano_assign("scat_mano_cloud_assign", nullptr, blend, joint_t, joint_s, weights_t, hands_mean, p, points, weights,
+                               max_dist, model_pts, nullptr, idx, dist, vw, vtarget, stats, B, N, V, parents, stream);
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label("mano_cloud_assign_v%d_n%d", V, N);
+    return SCAT_OK;
 }
 
 extern "C" int scat_mano_cloud_assign_plane(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
@@ -574,21 +470,9 @@ extern "C" int scat_mano_cloud_assign_plane(const float* blend, const float* joi
                                             float w_tangent, float* model_pts, float* normals, int* idx, float* dist, float* vw,
                                             float* vtarget, double* stats, int B, int N, int V, int F, uint64_t parents,
                                             void* stream) {
-    const char* fn = "scat_mano_cloud_assign_plane";
-    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, p, points, normals, idx, dist, vw, vtarget, stats};
-    CloudArgs a = {};
-    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
-    int rc = mano_validate(fn, ptrs, 13, B, V, parents, kNoTips, &a.m.levels);
-    if (rc != SCAT_OK) return rc;
-    const void* nullable[] = {weights, model_pts};
-    rc = cloud_check(fn, nullable, 2, stats, N, max_dist);
-    if (rc == SCAT_OK) rc = topo_check(fn, faces, vf_off, vf_idx, F);
-    if (rc == SCAT_OK) rc = tau_check(fn, w_tangent);
-    if (rc != SCAT_OK) return rc;
-    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist, a.model_pts = model_pts;
-    a.idx = idx, a.dist = dist, a.vw = vw, a.vtarget = vtarget, a.stats = stats, a.N = N, a.V = V;
-    a.faces = faces, a.vf_off = vf_off, a.vf_idx = vf_idx, a.F = F, a.w_tangent = w_tangent, a.normals = normals;
-    rc = cloud_launch<true, true>(fn, a, B, stream);
+    const CloudTopo topo = {faces, vf_off, vf_idx, F, w_tangent};
+    const int rc = mano_assign("scat_mano_cloud_assign_plane", &topo, blend, joint_t, joint_s, weights_t, hands_mean, p, points,
+                               weights, max_dist, model_pts, normals, idx, dist, vw, vtarget, stats, B, N, V, parents, stream);
     if (rc != SCAT_OK) return rc;
     set_kernel_label("mano_cloud_assign_plane_v%d_n%d_f%d", V, N, F);
     return SCAT_OK;
@@ -610,19 +494,188 @@ extern "C" int scat_mesh_normals(const float* verts, const int32_t* faces, const
     return SCAT_OK;
 }
 
+// The workspace of an ICP loop over B hands: byte offsets, every part rounded up to 16 bytes.  The normals [B,V,3] follow
+// the parts every loop has only in the plane form, and the track solve's workspace only for a track; a part that is not
+// there takes no bytes
+struct PointsWs { int64_t stats, vtarget, vw, cost, acc, idx, dist, normals, solve, total; };
 
-// ICP over a track of clouds, include/scat_mano_fit_seq_verts.h: points_loop's rounds with the S T frames as the
-// assignment's batch and mano_fit_seq_verts.hip's track solve in place of the per-hand fit.  The assignment's stats go to
-// the solve, which bridges a frame where nothing matched and refuses the sequence of an unusable one; the accepted counts
-// add up in the track kernel, so the assignment folds nothing (fold = 0).
+static PointsWs points_ws(int64_t B, int64_t N, int64_t V, bool plane, int64_t solve_bytes) {
+    PointsWs w;
+    int64_t off = 0;
+    const auto take = [&off](int64_t bytes) {
+        const int64_t o = off;
+        off += (bytes + 15) & ~(int64_t)15;
+        return o;
+    };
+    w.stats = take(B * 4 * (int64_t)sizeof(double));
+    w.vtarget = take(B * V * 3 * (int64_t)sizeof(float));
+    w.vw = take(B * V * (int64_t)sizeof(float));
+    w.cost = take(B * (int64_t)sizeof(float));
+    w.acc = take(B * (int64_t)sizeof(int));
+    w.idx = take(B * N * (int64_t)sizeof(int));
+    w.dist = take(B * N * (int64_t)sizeof(float));
+    w.normals = take(plane ? B * V * 3 * (int64_t)sizeof(float) : 0);
+    w.solve = take(solve_bytes);
+    w.total = off;
+    return w;
+}
+
+extern "C" int64_t scat_mano_fit_points_ws(int B, int N, int V) {
+    if (B < 1 || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV) return 0;
+    return points_ws(B, N, V, false, 0).total;
+}
+
+extern "C" int64_t scat_mano_fit_points_plane_ws(int B, int N, int V, int F) {
+    if (B < 1 || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV || F < 1 || F > SCAT_RENDER_MAX_F) return 0;
+    return points_ws(B, N, V, true, 0).total;
+}
+
 extern "C" int64_t scat_mano_fit_points_seq_ws(int S, int T, int N, int V, int F) {
     if (S < 1 || T < 1 || T > SCAT_FIT_SEQ_MAX_T || N < 1 || N > kPMaxN || V < 1 || V > kMMaxV || F < 0 || F > SCAT_RENDER_MAX_F)
         return 0;
     const int64_t B = (int64_t)S * T;
     if (B > INT32_MAX) return 0;   // S T is the assignment's batch and a grid size
-    return (F ? plane_ws_total(B, N, V) : points_ws(B, N, V).total) + seq_verts_ws_bytes(S, T, V);
+    return points_ws(B, N, V, F != 0, seq_verts_ws_bytes(S, T, V)).total;
 }
 
+// What an ICP entry point packs for icp_loop
+struct IcpCall {
+    const float *blend, *joint_t, *joint_s, *weights_t, *hands_mean;
+    const float* points;     // [B,N,3]
+    const float* weights;    // [B,N] or null
+    const CloudTopo* topo;   // null: nearest vertex; otherwise point-to-plane
+    float* p;                // [B,62]
+    float* data_cost;        // [B]
+    int* accepted;           // per hand [B], of a track [S]
+    int* idx;                // [B,N] or null
+    float* dist;             // [B,N] or null
+    void* ws;
+    int64_t ws_bytes;
+    int S, T;                // a track (smooth not null): B = S T; otherwise B = S hands and T is not looked at
+    int N, V;
+    uint64_t parents;
+    int rounds, iters;
+    float max_dist, lambda0, w_pose, w_beta;
+    const float* smooth;     // a track: its five weights, s_rots .. s_scale
+    uint64_t free_mask;
+    void* stream;
+};
+
+// The parts of the workspace that the solve between two assignments reads and writes
+struct IcpParts {
+    const float* vtarget;    // [B,V,3]
+    const float* vw;         // [B,V]
+    const float* normals;    // [B,V,3], or null without a topology
+    const double* stats;     // [B,4]
+    float* cost;             // [B]
+    int* acc;                // [B]
+    void* solve;             // the track solve's own workspace
+    int64_t solve_bytes;
+};
+
+// Every ICP loop: the checks, the workspace, then rounds x {assign, solve} and one last assign: 2 rounds + 1 launches of
+// the mesh fit, more of the track solve.  bind(parts) points the solve at the workspace and makes the solve's own checks,
+// once; solve(r) is the launches of round r, unchecked.  Per hand each assign after the first adds the accepted count of
+// the fit before it to the caller's total (fold); a track's counts add up in the track kernel
+template <class Bind, class Solve>
+static int icp_loop(const char* fn, const IcpCall& c, Bind&& bind, Solve&& solve) {
+    const bool track = c.smooth != nullptr;
+    const void* ptrs[] = {c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.points, c.p, c.data_cost, c.accepted};
+    ManoArgs m = fit_model_args(c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.V, c.parents, kNoTips);
+    int rc = mano_validate(fn, ptrs, 9, c.S, c.V, c.parents, kNoTips, &m.levels);
+    if (rc != SCAT_OK) return rc;
+    if (track) {
+        rc = seq_check_frames(fn, c.T);
+        if (rc != SCAT_OK) return rc;
+        SCAT_REQUIRE((int64_t)c.S * c.T <= INT32_MAX, SCAT_E_SHAPE, "%s: %d sequences of %d frames are more than %d frames in all", fn,
+                     c.S, c.T, INT32_MAX);
+    }
+    const void* nullable[] = {c.weights, c.idx, c.dist};
+    rc = cloud_check(fn, nullable, 3, nullptr, c.N, c.max_dist);
+    if (rc == SCAT_OK && c.topo) rc = topo_check(fn, c.topo->faces, c.topo->vf_off, c.topo->vf_idx, c.topo->F);
+    if (rc == SCAT_OK && c.topo) rc = fit_check_tau(fn, c.topo->w_tangent);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(c.rounds >= 1 && c.rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, c.rounds,
+                 SCAT_FIT_POINTS_MAX_ROUNDS);
+    rc = fit_check_solver(fn, "none: the start is the caller's", c.iters, 0, c.lambda0, c.w_pose, c.w_beta);
+    if (rc != SCAT_OK) return rc;
+    SCAT_REQUIRE(c.rounds * c.iters <= SCAT_FIT_POINTS_MAX_STEPS, SCAT_E_ARG, "%s: %d rounds of %d iterations are more than %d steps",
+                 fn, c.rounds, c.iters, SCAT_FIT_POINTS_MAX_STEPS);
+    if (track) rc = seq_check_smooth(fn, c.smooth, kSeqVertsSmooth, 5);
+    if (rc == SCAT_OK) rc = fit_check_mask(fn, c.free_mask);
+    if (rc != SCAT_OK) return rc;
+    const int B = track ? c.S * c.T : c.S;
+    const PointsWs w = points_ws(B, c.N, c.V, c.topo != nullptr, track ? seq_verts_ws_bytes(c.S, c.T, c.V) : 0);
+    rc = seq_check_ws(fn, c.ws, c.ws_bytes, w.total);
+    if (rc != SCAT_OK) return rc;
+
+    const auto part = [&c](int64_t off) { return static_cast<void*>(static_cast<char*>(c.ws) + off); };
+    float* const vtarget = static_cast<float*>(part(w.vtarget));
+    float* const vw = static_cast<float*>(part(w.vw));
+    float* const normals = c.topo ? static_cast<float*>(part(w.normals)) : nullptr;
+    double* const stats = static_cast<double*>(part(w.stats));
+    const IcpParts parts = {vtarget, vw, normals, stats, static_cast<float*>(part(w.cost)), static_cast<int*>(part(w.acc)),
+                            part(w.solve), c.ws_bytes - w.solve};
+    CloudArgs a = cloud_args(m, c.p, nullptr, c.points, c.weights, c.max_dist, nullptr, c.idx ? c.idx : static_cast<int*>(part(w.idx)),
+                             c.dist ? c.dist : static_cast<float*>(part(w.dist)), vw, vtarget, stats, c.N, c.V, c.topo, normals);
+    if (!track) a.acc_round = parts.acc, a.acc_total = c.accepted;
+    rc = bind(parts);
+    if (rc != SCAT_OK) return rc;
+    for (int r = 0; r <= c.rounds; ++r) {
+        a.fold = track ? 0 : r == 0 ? 1 : 2;   // 1 zeroes the total, 2 adds the round before
+        a.data_cost = r == c.rounds ? c.data_cost : nullptr;
+        rc = c.topo ? cloud_launch<true, true>(fn, a, B, c.stream) : cloud_launch<true>(fn, a, B, c.stream);
+        if (rc != SCAT_OK || r == c.rounds) return rc;
+        rc = solve(r);
+        if (rc != SCAT_OK) return rc;
+    }
+    return SCAT_OK;
+}
+
+// Both per-hand loops: icp_loop around the mesh fit, the metric one with a topology
+static int hand_icp(const char* fn, const char* label, const IcpCall& c) {
+    VertsCall v = {c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, nullptr, nullptr, nullptr, c.p, nullptr, nullptr, c.S, c.V,
+                   c.parents, c.iters, 0, c.topo != nullptr, c.topo ? c.topo->w_tangent : 1.f, c.lambda0, c.w_pose, c.w_beta,
+                   c.free_mask, 0, c.stream};
+    int levels = 0;
+    const int rc = icp_loop(
+        fn, c,
+        [&](const IcpParts& w) {
+            v.targets = w.vtarget, v.weights = w.vw, v.normals = w.normals, v.cost = w.cost, v.accepted = w.acc;
+            return fit_verts_check(fn, v, &levels);
+        },
+        [&](int) { return fit_verts_launch(fn, v, levels); });
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label(label, c.V, c.N, c.rounds, c.iters);
+    return SCAT_OK;
+}
+
+extern "C" int scat_mano_fit_points(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                    const float* hands_mean, const float* points, const float* weights, float* p,
+                                    float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
+                                    int N, int V, uint64_t parents, int rounds, int iters, float max_dist, float lambda0,
+                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
+    return hand_icp("scat_mano_fit_points", "mano_fit_points_v%d_n%d_r%d_i%d",
+                    {blend, joint_t, joint_s, weights_t, hands_mean, points, weights, nullptr, p, data_cost, accepted, idx, dist, ws,
+                     ws_bytes, B, 0, N, V, parents, rounds, iters, max_dist, lambda0, w_pose, w_beta, nullptr, free_mask, stream});
+}
+
+extern "C" int scat_mano_fit_points_plane(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
+                                          const float* hands_mean, const float* points, const float* weights,
+                                          const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, float* p,
+                                          float* data_cost, int* accepted, int* idx, float* dist, void* ws, int64_t ws_bytes, int B,
+                                          int N, int V, int F, uint64_t parents, int rounds, int iters, float max_dist,
+                                          float w_tangent, float lambda0, float w_pose, float w_beta, uint64_t free_mask,
+                                          void* stream) {
+    const CloudTopo topo = {faces, vf_off, vf_idx, F, w_tangent};
+    return hand_icp("scat_mano_fit_points_plane", "mano_fit_points_plane_v%d_n%d_r%d_i%d",
+                    {blend, joint_t, joint_s, weights_t, hands_mean, points, weights, &topo, p, data_cost, accepted, idx, dist, ws,
+                     ws_bytes, B, 0, N, V, parents, rounds, iters, max_dist, lambda0, w_pose, w_beta, nullptr, free_mask, stream});
+}
+
+// ICP over a track of clouds, include/scat_mano_fit_seq_verts.h: icp_loop with the S T frames as the assignment's batch and
+// mano_fit_seq_verts.hip's track solve in place of the per-hand fit.  The assignment's stats go to the solve, which bridges
+// a frame where nothing matched and refuses the sequence of an unusable one
 extern "C" int scat_mano_fit_points_seq(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
                                         const float* hands_mean, const float* points, const float* weights, const int32_t* faces,
                                         const int32_t* vf_off, const int32_t* vf_idx, float* p, float* data_cost, int* accepted,
@@ -631,66 +684,27 @@ extern "C" int scat_mano_fit_points_seq(const float* blend, const float* joint_t
                                         float w_pose, float w_beta, float s_rots, float s_poses, float s_betas, float s_trans,
                                         float s_scale, uint64_t free_mask, void* stream) {
     const char* fn = "scat_mano_fit_points_seq";
-    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, points, p, data_cost, accepted};
-    CloudArgs a = {};
-    a.m = fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips);
-    int rc = mano_validate(fn, ptrs, 9, S, V, parents, kNoTips, &a.m.levels);
-    if (rc != SCAT_OK) return rc;
-    rc = seq_check_frames(fn, T);
-    if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE((int64_t)S * T <= INT32_MAX, SCAT_E_SHAPE, "%s: %d sequences of %d frames are more than %d frames in all", fn, S, T,
-                 INT32_MAX);
-    const void* nullable[] = {weights, idx, dist};
-    rc = cloud_check(fn, nullable, 3, nullptr, N, max_dist);
-    if (rc != SCAT_OK) return rc;
+    const CloudTopo topo = {faces, vf_off, vf_idx, F, w_tangent};
     const bool plane = faces || vf_off || vf_idx || F != 0;
-    if (plane) {
-        rc = topo_check(fn, faces, vf_off, vf_idx, F);
-        if (rc == SCAT_OK) rc = tau_check(fn, w_tangent);
-        if (rc != SCAT_OK) return rc;
-    }
-    SCAT_REQUIRE(rounds >= 1 && rounds <= SCAT_FIT_POINTS_MAX_ROUNDS, SCAT_E_ARG, "%s: %d rounds outside 1..%d", fn, rounds,
-                 SCAT_FIT_POINTS_MAX_ROUNDS);
-    rc = fit_check_solver(fn, "none: the start is the caller's", iters, 0, lambda0, w_pose, w_beta);
+    SeqVertsCall q = {blend, joint_t, joint_s, weights_t, hands_mean, nullptr, nullptr, nullptr, nullptr, p, nullptr, accepted,
+                      nullptr, 0, S, T, V, parents, iters, 0, w_tangent, lambda0, w_pose, w_beta,
+                      {s_rots, s_poses, s_betas, s_trans, s_scale}, free_mask, 0, stream};
+    const IcpCall c = {blend, joint_t, joint_s, weights_t, hands_mean, points, weights, plane ? &topo : nullptr, p, data_cost, accepted,
+                       idx, dist, ws, ws_bytes, S, T, N, V, parents, rounds, iters, max_dist, lambda0, w_pose, w_beta, q.smooth,
+                       free_mask, stream};
+    int levels = 0;
+    const int rc = icp_loop(
+        fn, c,
+        [&](const IcpParts& w) {
+            q.targets = w.vtarget, q.weights = w.vw, q.normals = w.normals, q.stats = w.stats, q.cost = w.cost;
+            q.ws = w.solve, q.ws_bytes = w.solve_bytes;
+            return seq_verts_check(fn, q, &levels);
+        },
+        [&](int r) {
+            q.acc_add = r > 0;
+            return seq_verts_launch(fn, q, levels);
+        });
     if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(rounds * iters <= SCAT_FIT_POINTS_MAX_STEPS, SCAT_E_ARG, "%s: %d rounds of %d iterations are more than %d steps",
-                 fn, rounds, iters, SCAT_FIT_POINTS_MAX_STEPS);
-    const float sw[5] = {s_rots, s_poses, s_betas, s_trans, s_scale};
-    const char* const sn[5] = {"s_rots", "s_poses", "s_betas", "s_trans", "s_scale"};
-    rc = seq_check_smooth(fn, sw, sn, 5);
-    if (rc != SCAT_OK) return rc;
-    rc = fit_check_mask(fn, free_mask);
-    if (rc != SCAT_OK) return rc;
-    rc = seq_check_ws(fn, ws, ws_bytes, scat_mano_fit_points_seq_ws(S, T, N, V, F));
-    if (rc != SCAT_OK) return rc;
-
-    const int B = S * T;
-    const PointsWs w = points_ws(B, N, V);
-    const int64_t cloud_bytes = plane ? plane_ws_total(B, N, V) : w.total;
-    char* base = static_cast<char*>(ws);
-    a.p = p, a.points = points, a.weights = weights, a.max_dist = max_dist;
-    a.idx = idx ? idx : reinterpret_cast<int*>(base + w.idx);
-    a.dist = dist ? dist : reinterpret_cast<float*>(base + w.dist);
-    a.vw = reinterpret_cast<float*>(base + w.vw), a.vtarget = reinterpret_cast<float*>(base + w.vtarget);
-    a.stats = reinterpret_cast<double*>(base + w.stats);
-    a.fold = 0, a.N = N, a.V = V;
-    if (plane) {
-        a.faces = faces, a.vf_off = vf_off, a.vf_idx = vf_idx, a.F = F, a.w_tangent = w_tangent;
-        a.normals = reinterpret_cast<float*>(base + w.total);
-    }
-    SeqVertsCall c = {blend, joint_t, joint_s, weights_t, hands_mean, a.vtarget, a.vw, plane ? a.normals : nullptr, a.stats, p,
-                      reinterpret_cast<float*>(base + w.cost), accepted, base + cloud_bytes, ws_bytes - cloud_bytes, S, T, V,
-                      parents, iters, 0, w_tangent, lambda0, w_pose, w_beta, {s_rots, s_poses, s_betas, s_trans, s_scale},
-                      free_mask, 0, stream};
-    for (int r = 0; r <= rounds; ++r) {
-        a.data_cost = r == rounds ? data_cost : nullptr;
-        rc = plane ? cloud_launch<true, true>(fn, a, B, stream) : cloud_launch<true>(fn, a, B, stream);
-        if (rc != SCAT_OK) return rc;
-        if (r == rounds) break;
-        c.acc_add = r > 0;
-        rc = seq_verts_solve(fn, nullptr, c);
-        if (rc != SCAT_OK) return rc;
-    }
     set_kernel_label(plane ? "mano_fit_points_seq_plane_v%d_n%d_t%d_r%d_i%d" : "mano_fit_points_seq_v%d_n%d_t%d_r%d_i%d", V, N, T,
                      rounds, iters);
     return SCAT_OK;

@@ -1,6 +1,7 @@
-// The track solve of mano_fit_seq_verts.hip as the library's own callers see it: scat_mano_fit_seq_verts is this with
-// stats = null and acc_add = 0; the ICP loop over a track of clouds (mano_fit_points.hip) passes the assignment's stats and
-// lets the accepted counts add up over its rounds.
+// The track solve of mano_fit_seq_verts.hip as the library's own callers see it: scat_mano_fit_seq_verts is
+// seq_verts_check, then seq_verts_launch, with stats = null and acc_add = 0; the ICP loop over a track of clouds
+// (mano_fit_points.hip) checks once, launches once per round, passes the assignment's stats and lets the accepted counts
+// add up over its rounds.
 #pragma once
 #include <stdint.h>
 
@@ -26,9 +27,13 @@ struct SeqVertsCall {
     void* stream;
 };
 
-// the bytes of workspace seq_verts_solve needs; 0 for sizes it refuses
+// the names of smooth[] in the errors
+static const char* const kSeqVertsSmooth[5] = {"s_rots", "s_poses", "s_betas", "s_trans", "s_scale"};
+
+// the bytes of workspace the solve needs; 0 for sizes it refuses
 int64_t seq_verts_ws_bytes(int S, int T, int V);
 
-// every check, then the launches.  fn: the entry point named in the errors; label: set_kernel_label's format for (V, T, iters)
-// or null for none
-int seq_verts_solve(const char* fn, const char* label, const SeqVertsCall& c);
+// every check.  fn: the entry point named in the errors; *levels: the depth of the joint tree, which the launches take
+int seq_verts_check(const char* fn, const SeqVertsCall& c, int* levels);
+// the 2 iters + 2 launches (two more with init), no check but the launches' own
+int seq_verts_launch(const char* fn, const SeqVertsCall& c, int levels);

@@ -15,11 +15,14 @@
 // A_t, g_t stand undamped in two buffers, the current point's and the trial's, that swap with the unknowns' on an accepted
 // step: a rejected step re-solves from what is there.  Everything a later launch needs of an earlier one is in the
 // workspace; the stream orders them.  No atomics; every sum in an order fixed by the sizes.
+// Host: seq_verts_check is every refusal, seq_verts_launch the 2 iters + 2 launches (mano_fit_seq_verts.h); the entry point
+// runs both, the ICP loop over a track of clouds (mano_fit_points.hip) the first once and the second once per round.
 #include "mano_fit_seq_common.h"
 #include "mano_fit_verts_common.h"
 
 #include "../../include/scat_mano_fit_seq_verts.h"
 #include "mano_fit_seq_verts.h"
+#include "mano_fit_verts.h"
 
 namespace scat {
 
@@ -129,9 +132,8 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_seq_verts_frame_kernel(SVA
     }
 
     vj_ancestors(m, a.m.parents);
-    int bi0 = 0;   // this thread's block of [J r]^T [J r]: rows 3 bi0.., columns 3 bj0.., bj0 <= bi0
-    while ((bi0 + 1) * (bi0 + 2) / 2 <= tid) ++bi0;
-    const int bj0 = tid - bi0 * (bi0 + 1) / 2;
+    int bi0, bj0;   // this thread's block of [J r]^T [J r]
+    vfit_block(tid, bi0, bj0);
     const bool cost_owner = tid == kVOwners - 1;   // block (20, 20): entry (62, 62) is the data cost
     double tot[3][3], cst = 0.0;
 #pragma unroll
@@ -420,11 +422,9 @@ int64_t seq_verts_ws_bytes(int S, int T, int V) {
     return seq_verts_layout(S, T).total;
 }
 
-int seq_verts_solve(const char* fn, const char* label, const SeqVertsCall& c) {
+int seq_verts_check(const char* fn, const SeqVertsCall& c, int* levels) {
     const void* ptrs[] = {c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.targets, c.p, c.cost, c.accepted};
-    SVArgs a = {};
-    a.m = fit_model_args(c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.V, c.parents, kNoTips);
-    int rc = mano_validate(fn, ptrs, 9, c.S, c.V, c.parents, kNoTips, &a.m.levels);
+    int rc = mano_validate(fn, ptrs, 9, c.S, c.V, c.parents, kNoTips, levels);
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE((((uintptr_t)c.weights | (uintptr_t)c.normals) & 3) == 0, SCAT_E_ARG, "%s: fp32 operands must be 4-byte aligned", fn);
     SCAT_REQUIRE(((uintptr_t)c.stats & 7) == 0, SCAT_E_ARG, "%s: stats must be 8-byte aligned", fn);
@@ -435,16 +435,17 @@ int seq_verts_solve(const char* fn, const char* label, const SeqVertsCall& c) {
     rc = fit_check_solver(fn, "Procrustes over the vertices, frame by frame", c.iters, c.init, c.lambda0, c.w_pose, c.w_beta);
     if (rc != SCAT_OK) return rc;
     SCAT_REQUIRE(!(c.init && c.normals), SCAT_E_ARG, "%s: init 1 is the Euclidean fit's: with normals the start is the caller's", fn);
-    if (c.normals)
-        SCAT_REQUIRE(c.w_tangent >= 0.f && c.w_tangent <= 1.f, SCAT_E_ARG, "%s: w_tangent %g outside 0..1", fn, (double)c.w_tangent);
-    const char* const sn[5] = {"s_rots", "s_poses", "s_betas", "s_trans", "s_scale"};
-    rc = seq_check_smooth(fn, c.smooth, sn, 5);
-    if (rc != SCAT_OK) return rc;
-    rc = fit_check_mask(fn, c.free_mask);
-    if (rc != SCAT_OK) return rc;
-    rc = seq_check_ws(fn, c.ws, c.ws_bytes, seq_verts_ws_bytes(c.S, c.T, c.V));
-    if (rc != SCAT_OK) return rc;
+    if (c.normals) rc = fit_check_tau(fn, c.w_tangent);
+    if (rc == SCAT_OK) rc = seq_check_smooth(fn, c.smooth, kSeqVertsSmooth, 5);
+    if (rc == SCAT_OK) rc = fit_check_mask(fn, c.free_mask);
+    if (rc == SCAT_OK) rc = seq_check_ws(fn, c.ws, c.ws_bytes, seq_verts_ws_bytes(c.S, c.T, c.V));
+    return rc;
+}
 
+int seq_verts_launch(const char* fn, const SeqVertsCall& c, int levels) {
+    SVArgs a = {};
+    a.m = fit_model_args(c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.V, c.parents, kNoTips);
+    a.m.levels = levels;
     const SeqVertsWs w = seq_verts_layout(c.S, c.T);
     char* base = static_cast<char*>(c.ws);
     a.targets = c.targets, a.weights = c.weights, a.normals = c.normals, a.stats = c.stats;
@@ -484,7 +485,6 @@ int seq_verts_solve(const char* fn, const char* label, const SeqVertsCall& c) {
     }
     track(kSVAssemble, 0, 1);
     SCAT_LAUNCH_CHECK(fn);
-    if (label) set_kernel_label(label, c.V, c.T, c.iters);
     return SCAT_OK;
 }
 
@@ -501,6 +501,11 @@ extern "C" int scat_mano_fit_seq_verts(const float* blend, const float* joint_t,
     const SeqVertsCall c = {blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, normals, nullptr, p, cost, accepted,
                             ws, ws_bytes, S, T, V, parents, iters, init, w_tangent, lambda0, w_pose, w_beta,
                             {s_rots, s_poses, s_betas, s_trans, s_scale}, free_mask, 0, stream};
-    return seq_verts_solve("scat_mano_fit_seq_verts", normals ? "mano_fit_seq_verts_metric_v%d_t%d_i%d" : "mano_fit_seq_verts_v%d_t%d_i%d",
-                           c);
+    const char* fn = "scat_mano_fit_seq_verts";
+    int levels = 0;
+    int rc = seq_verts_check(fn, c, &levels);
+    if (rc == SCAT_OK) rc = seq_verts_launch(fn, c, levels);
+    if (rc != SCAT_OK) return rc;
+    set_kernel_label(normals ? "mano_fit_seq_verts_metric_v%d_t%d_i%d" : "mano_fit_seq_verts_v%d_t%d_i%d", V, T, iters);
+    return SCAT_OK;
 }

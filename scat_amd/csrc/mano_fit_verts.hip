@@ -22,10 +22,14 @@
 // normal n.  The work-item that wrote the columns of a vertex into the tile takes them through sqrt(M) = a I + (1 - a) n n^T
 // in place, three entries of a column at a time, before the tile's barrier: no barrier and no LDS is added, and the
 // accumulation, the solve and accept / commit do not know.  vfit_cost sums rho instead of |r|^2.
+//
+// Host: both entry points pack a VertsCall (mano_fit_verts.h) for fit_verts_check, every refusal, and fit_verts_launch, the
+// kernel; the ICP loop of mano_fit_points.hip checks once and launches once per round.
 #include "mano_fit_verts_common.h"
 
 #include "../../include/scat_mano_fit_plane.h"
 #include "../../include/scat_mano_fit_verts.h"
+#include "mano_fit_verts.h"
 
 namespace scat {
 
@@ -180,9 +184,8 @@ __global__ __launch_bounds__(kFThreads) void mano_fit_verts_kernel(VFitArgs a) {
     vfit_cost<kMetric>(m, f, pc, f.p, tgt, wts, a.w_pose, a.w_beta, nrm, tau);
     if (tid == 0) f.cost = f.ct;
     const uint64_t fm = a.free_mask;
-    int bi0 = 0;   // this thread's block of [J r]^T [J r]: rows 3 bi0.., columns 3 bj0.., bj0 <= bi0
-    while ((bi0 + 1) * (bi0 + 2) / 2 <= tid) ++bi0;
-    const int bj0 = tid - bi0 * (bi0 + 1) / 2;
+    int bi0, bj0;   // this thread's block of [J r]^T [J r]
+    vfit_block(tid, bi0, bj0);
     for (int it = 0; it < a.iters; ++it) {
         vj_setup(m, pc, 0, true);
         const float sc = expf(f.p[kFU - 1]);
@@ -306,33 +309,53 @@ extern "C" int scat_mano_verts_jac(const float* blend, const float* joint_t, con
     return SCAT_OK;
 }
 
-// Both fits' entry points: the checks, then the kernel with `tile` vertices per tile (kVTile in the product; the others
-// are compiled into the diag build only)
-static int fit_verts_launch(const char* fn, const float* blend, const float* joint_t, const float* joint_s,
-                            const float* weights_t, const float* hands_mean, const float* targets, const float* weights,
-                            float* p, float* cost, int* accepted, int B, int V, uint64_t parents, int iters, int init,
-                            float lambda0, float w_pose, float w_beta, uint64_t free_mask, int tile, void* stream) {
-    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, targets, p, cost, accepted};
-    VFitArgs a = {fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips),
-                  targets, weights, p, cost, accepted, iters, init, lambda0, w_pose, w_beta, free_mask, nullptr, 1.f};
-    int rc = mano_validate(fn, ptrs, 9, B, V, parents, kNoTips, &a.m.levels);
+int fit_check_tau(const char* fn, float w_tangent) {
+    SCAT_REQUIRE(w_tangent >= 0.f && w_tangent <= 1.f, SCAT_E_ARG, "%s: w_tangent %g outside 0..1", fn, (double)w_tangent);
+    return SCAT_OK;
+}
+
+int fit_verts_check(const char* fn, const VertsCall& c, int* levels) {
+    const void* ptrs[] = {c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.targets, c.p, c.cost, c.accepted, c.normals};
+    int rc = mano_validate(fn, ptrs, c.metric ? 10 : 9, c.B, c.V, c.parents, kNoTips, levels);
     if (rc != SCAT_OK) return rc;
-    rc = fit_check_args(fn, "Procrustes over the vertices", weights, iters, init, lambda0, w_pose, w_beta, free_mask);
-    if (rc != SCAT_OK) return rc;
-    const dim3 grid(B), block(kFThreads);
-    if (tile == kVTile) {
-        hipLaunchKernelGGL((mano_fit_verts_kernel<kVTile, false>), grid, block, 0, (hipStream_t)stream, a);
-        set_kernel_label("mano_fit_verts_v%d_i%d", V, iters);
+    rc = fit_check_args(fn, c.metric ? "none: the start is the caller's" : "Procrustes over the vertices", c.weights, c.iters, c.init,
+                        c.lambda0, c.w_pose, c.w_beta, c.free_mask);
+    if (rc == SCAT_OK && c.metric) rc = fit_check_tau(fn, c.w_tangent);
+    return rc;
+}
+
+// the kernel with c.tile vertices per tile (0: kVTile, the product's; the others are compiled into the diag build only)
+int fit_verts_launch(const char* fn, const VertsCall& c, int levels) {
+    VFitArgs a = {fit_model_args(c.blend, c.joint_t, c.joint_s, c.weights_t, c.hands_mean, c.V, c.parents, kNoTips),
+                  c.targets, c.weights, c.p, c.cost, c.accepted, c.iters, c.init, c.lambda0, c.w_pose, c.w_beta, c.free_mask,
+                  c.metric ? c.normals : nullptr, c.metric ? c.w_tangent : 1.f};
+    a.m.levels = levels;
+    const dim3 grid(c.B), block(kFThreads);
+    hipStream_t stream = (hipStream_t)c.stream;
+    if (c.tile == 0 || c.tile == kVTile) {
+        if (c.metric) hipLaunchKernelGGL((mano_fit_verts_kernel<kVTile, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mano_fit_verts_kernel<kVTile, false>), grid, block, 0, stream, a);
 #ifdef SCAT_DIAG
-    } else if (tile == 8 || tile == 16) {
-        if (tile == 8) hipLaunchKernelGGL((mano_fit_verts_kernel<8, false>), grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((mano_fit_verts_kernel<16, false>), grid, block, 0, (hipStream_t)stream, a);
-        set_kernel_label("mano_fit_verts_v%d_i%d_t%d", V, iters, tile);
+    } else if ((c.tile == 8 || c.tile == 16) && !c.metric) {
+        if (c.tile == 8) hipLaunchKernelGGL((mano_fit_verts_kernel<8, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mano_fit_verts_kernel<16, false>), grid, block, 0, stream, a);
 #endif
     } else {
-        SCAT_REQUIRE(false, SCAT_E_ARG, "%s: no kernel with a tile of %d vertices", fn, tile);
+        SCAT_REQUIRE(false, SCAT_E_ARG, "%s: no kernel with a tile of %d vertices", fn, c.tile);
     }
     SCAT_LAUNCH_CHECK(fn);
+    return SCAT_OK;
+}
+
+// The public entry points: the checks, the launch, the label
+static int fit_verts_entry(const char* fn, const VertsCall& c) {
+    int levels = 0;
+    int rc = fit_verts_check(fn, c, &levels);
+    if (rc == SCAT_OK) rc = fit_verts_launch(fn, c, levels);
+    if (rc != SCAT_OK) return rc;
+    if (c.metric) set_kernel_label("mano_fit_verts_metric_v%d_i%d", c.V, c.iters);
+    else if (c.tile == 0 || c.tile == kVTile) set_kernel_label("mano_fit_verts_v%d_i%d", c.V, c.iters);
+    else set_kernel_label("mano_fit_verts_v%d_i%d_t%d", c.V, c.iters, c.tile);
     return SCAT_OK;
 }
 
@@ -340,8 +363,9 @@ extern "C" int scat_mano_fit_verts(const float* blend, const float* joint_t, con
                                    const float* hands_mean, const float* targets, const float* weights, float* p, float* cost,
                                    int* accepted, int B, int V, uint64_t parents, int iters, int init, float lambda0,
                                    float w_pose, float w_beta, uint64_t free_mask, void* stream) {
-    return fit_verts_launch("scat_mano_fit_verts", blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, p, cost,
-                            accepted, B, V, parents, iters, init, lambda0, w_pose, w_beta, free_mask, kVTile, stream);
+    return fit_verts_entry("scat_mano_fit_verts", {blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, nullptr, p, cost,
+                                                   accepted, B, V, parents, iters, init, 0, 1.f, lambda0, w_pose, w_beta, free_mask,
+                                                   0, stream});
 }
 
 extern "C" int scat_mano_fit_verts_metric(const float* blend, const float* joint_t, const float* joint_s, const float* weights_t,
@@ -349,19 +373,9 @@ extern "C" int scat_mano_fit_verts_metric(const float* blend, const float* joint
                                           const float* normals, float* p, float* cost, int* accepted, int B, int V,
                                           uint64_t parents, int iters, float w_tangent, float lambda0, float w_pose,
                                           float w_beta, uint64_t free_mask, void* stream) {
-    const char* fn = "scat_mano_fit_verts_metric";
-    const void* ptrs[] = {blend, joint_t, joint_s, weights_t, hands_mean, targets, normals, p, cost, accepted};
-    VFitArgs a = {fit_model_args(blend, joint_t, joint_s, weights_t, hands_mean, V, parents, kNoTips),
-                  targets, weights, p, cost, accepted, iters, 0, lambda0, w_pose, w_beta, free_mask, normals, w_tangent};
-    int rc = mano_validate(fn, ptrs, 10, B, V, parents, kNoTips, &a.m.levels);
-    if (rc != SCAT_OK) return rc;
-    rc = fit_check_args(fn, "none: the start is the caller's", weights, iters, 0, lambda0, w_pose, w_beta, free_mask);
-    if (rc != SCAT_OK) return rc;
-    SCAT_REQUIRE(w_tangent >= 0.f && w_tangent <= 1.f, SCAT_E_ARG, "%s: w_tangent %g outside 0..1", fn, (double)w_tangent);
-    hipLaunchKernelGGL((mano_fit_verts_kernel<kVTile, true>), dim3(B), dim3(kFThreads), 0, (hipStream_t)stream, a);
-    SCAT_LAUNCH_CHECK(fn);
-    set_kernel_label("mano_fit_verts_metric_v%d_i%d", V, iters);
-    return SCAT_OK;
+    return fit_verts_entry("scat_mano_fit_verts_metric", {blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, normals, p,
+                                                          cost, accepted, B, V, parents, iters, 0, 1, w_tangent, lambda0, w_pose,
+                                                          w_beta, free_mask, 0, stream});
 }
 
 #ifdef SCAT_DIAG
@@ -371,7 +385,8 @@ extern "C" int scat_mano_fit_verts_tile(const float* blend, const float* joint_t
                                         const float* hands_mean, const float* targets, const float* weights, float* p,
                                         float* cost, int* accepted, int B, int V, uint64_t parents, int iters, int init,
                                         float lambda0, float w_pose, float w_beta, uint64_t free_mask, int tile, void* stream) {
-    return fit_verts_launch("scat_mano_fit_verts_tile", blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, p,
-                            cost, accepted, B, V, parents, iters, init, lambda0, w_pose, w_beta, free_mask, tile, stream);
+    return fit_verts_entry("scat_mano_fit_verts_tile", {blend, joint_t, joint_s, weights_t, hands_mean, targets, weights, nullptr, p,
+                                                        cost, accepted, B, V, parents, iters, init, 0, 1.f, lambda0, w_pose, w_beta,
+                                                        free_mask, tile, stream});
 }
 #endif

@@ -1,8 +1,10 @@
 // What the mesh kernels share (mano_fit_verts.hip: one hand per workgroup, solver included; mano_fit_seq_verts.hip: one
 // frame of a track per workgroup, no solver): the tile constants, the staged tile VertStage, the pose state with the
 // derivatives the columns are built from (vj_ancestors, vj_derivs, vj_setup), the blend and skinning of a tile (vj_stage),
-// the columns of a vertex (vj_cols), the square root of the plane metric on a column (vfit_sqrt_metric) and the Procrustes
-// start over the vertices (vfit_procrustes).  mano_fit_verts.hip's header comment has the derivation of the columns.
+// the columns of a vertex (vj_cols), the square root of the plane metric on a column (vfit_sqrt_metric), the 3 x 3 block of
+// the normal equations that a thread owns (vfit_block) and the Procrustes start over the vertices (vfit_procrustes).
+// mano_fit_verts.hip's header comment has the derivation of the columns.  The tile walk that fills the blocks and the fp64
+// sum of the priors stand written out in both kernels, on purpose: profiles/fit_mesh_cloud_refactor.txt, section A.
 #pragma once
 #include "mano_fit_common.h"
 
@@ -277,6 +279,14 @@ __device__ __forceinline__ void vfit_sqrt_metric(float* c, int ld, const float n
     c[0] = a * c0 + k * n[0];
     c[ld] = a * c1 + k * n[1];
     c[2 * ld] = a * c2 + k * n[2];
+}
+
+// The 3 x 3 block of the lower triangle of [J r]^T [J r] that thread tid < kVOwners keeps: rows 3 bi0.., columns 3 bj0..,
+// bj0 <= bi0.  The last owner's is block (20, 20), whose entry (62, 62) is the data cost
+__device__ __forceinline__ void vfit_block(int tid, int& bi0, int& bj0) {
+    bi0 = 0;
+    while ((bi0 + 1) * (bi0 + 2) / 2 <= tid) ++bi0;
+    bj0 = tid - bi0 * (bi0 + 1) / 2;
 }
 
 // init = 1: rots, trans, log_scale of the weighted similarity that takes the zero-pose vertices onto the targets.  The

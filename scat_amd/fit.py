@@ -343,21 +343,31 @@ def mano_cloud_assign(model, p, points, weights, max_dist, want_model_pts=False)
     return (c, mp) if want_model_pts else c
 
 
+def _icp_launch(query, entry, model, points, weights, topo_ptrs, p, n_accepted, sizes, tail):
+    """The launch of every ICP loop: allocates data_cost (the points' leading shape), accepted [n_accepted], idx, dist and
+    the workspace, at the size query(*sizes) gives (0 for sizes the launch refuses), and calls entry with the model, points,
+    weights, topo_ptrs, p, these, sizes, the tree and tail -> (data_cost, accepted int32, idx int32, dist, stats [...,4] fp64
+    of the last assignment, which is the head of the workspace)"""
+    lead, N, dev = tuple(int(n) for n in points.shape[:-2]), int(points.shape[-2]), points.device
+    hands = math.prod(lead)
+    cost = torch.empty(lead, dtype=torch.float32, device=dev)
+    accepted = torch.empty((n_accepted,), dtype=torch.int32, device=dev)
+    idx = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
+    dist = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+    ws, nbytes = _workspace(query, sizes, dev, max(32 * hands, 16))
+    entry(*_model_args(model), _p(points), _p(weights), *topo_ptrs, _p(p), _p(cost), _p(accepted), _p(idx), _p(dist), _p(ws), nbytes,
+          *sizes, model.parents_packed, *tail, _stream())
+    return cost, accepted, idx, dist, ws[:32 * hands].view(torch.float64).reshape(*lead, 4).clone()
+
+
 def mano_fit_points(model, points, weights, p, rounds, iters, max_dist, lambda0, w_pose, w_beta, free=ALL_FREE):
     """scat_mano_fit_points as it is declared: points [B,N,3], weights [B,N] or None, p [B,62] read and written ->
     (data_cost [B], accepted [B] int32, idx [B,N] int32, dist [B,N], stats [B,4] fp64 of the last assignment).  The
     workspace is allocated here, at the size scat_mano_fit_points_ws gives (0 for sizes the launch refuses)."""
     B, N = int(points.shape[0]), int(points.shape[1])
-    dev = points.device
-    cost, accepted = _results(B, dev)
-    idx = torch.empty((B, N), dtype=torch.int32, device=dev)
-    dist = torch.empty((B, N), dtype=torch.float32, device=dev)
     ns = lib().bind(FIT_POINTS_HEADER)
-    ws, nbytes = _workspace(ns.scat_mano_fit_points_ws, (B, N, model.V), dev, max(32 * B, 16))
-    ns.scat_mano_fit_points(*_model_args(model), _p(points), _p(weights), _p(p), _p(cost), _p(accepted), _p(idx), _p(dist), _p(ws),
-                            nbytes, B, N, model.V, model.parents_packed, int(rounds), int(iters), float(max_dist), float(lambda0),
-                            float(w_pose), float(w_beta), int(free), _stream())
-    return cost, accepted, idx, dist, ws[:32 * B].view(torch.float64).reshape(B, 4).clone()
+    return _icp_launch(ns.scat_mano_fit_points_ws, ns.scat_mano_fit_points, model, points, weights, (), p, B, (B, N, model.V),
+                       (int(rounds), int(iters), float(max_dist), float(lambda0), float(w_pose), float(w_beta), int(free)))
 
 
 class Topology(NamedTuple):
@@ -416,17 +426,10 @@ def mano_fit_points_plane(model, points, weights, topo, p, rounds, iters, max_di
     plane metric, accepted [B] int32, idx [B,N] int32, dist [B,N], stats [B,4] fp64 of the last assignment).  The workspace
     is allocated here, at the size scat_mano_fit_points_plane_ws gives (0 for sizes the launch refuses)."""
     B, N = int(points.shape[0]), int(points.shape[1])
-    dev = points.device
-    cost, accepted = _results(B, dev)
-    idx = torch.empty((B, N), dtype=torch.int32, device=dev)
-    dist = torch.empty((B, N), dtype=torch.float32, device=dev)
     ns = lib().bind(FIT_PLANE_HEADER)
-    ws, nbytes = _workspace(ns.scat_mano_fit_points_plane_ws, (B, N, model.V, topo.F), dev, max(32 * B, 16))
-    ns.scat_mano_fit_points_plane(*_model_args(model), _p(points), _p(weights), *topo.ptrs, _p(p), _p(cost), _p(accepted), _p(idx),
-                                  _p(dist), _p(ws), nbytes, B, N, model.V, topo.F, model.parents_packed, int(rounds), int(iters),
-                                  float(max_dist), float(w_tangent), float(lambda0), float(w_pose), float(w_beta), int(free),
-                                  _stream())
-    return cost, accepted, idx, dist, ws[:32 * B].view(torch.float64).reshape(B, 4).clone()
+    return _icp_launch(ns.scat_mano_fit_points_plane_ws, ns.scat_mano_fit_points_plane, model, points, weights, topo.ptrs, p, B,
+                       (B, N, model.V, topo.F), (int(rounds), int(iters), float(max_dist), float(w_tangent), float(lambda0),
+                                                 float(w_pose), float(w_beta), int(free)))
 
 
 def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
@@ -482,19 +485,11 @@ def mano_fit_points_seq(model, points, weights, topo, p, rounds, iters, max_dist
     stats [S,T,4] fp64 of the last assignment).  The workspace is allocated here, at the size scat_mano_fit_points_seq_ws
     gives (0 for sizes the launch refuses)."""
     S, T, N = (int(n) for n in points.shape[:3])
-    dev = points.device
-    cost = torch.empty((S, T), dtype=torch.float32, device=dev)
-    accepted = torch.empty((S,), dtype=torch.int32, device=dev)
-    idx = torch.empty((S, T, N), dtype=torch.int32, device=dev)
-    dist = torch.empty((S, T, N), dtype=torch.float32, device=dev)
     ns = lib().bind(FIT_SEQ_VERTS_HEADER)
-    F = 0 if topo is None else topo.F
-    ws, nbytes = _workspace(ns.scat_mano_fit_points_seq_ws, (S, T, N, model.V, F), dev, max(32 * S * T, 16))
-    ns.scat_mano_fit_points_seq(*_model_args(model), _p(points), _p(weights), *((0, 0, 0) if topo is None else topo.ptrs), _p(p),
-                                _p(cost), _p(accepted), _p(idx), _p(dist), _p(ws), nbytes, S, T, N, model.V, F,
-                                model.parents_packed, int(rounds), int(iters), float(max_dist), float(w_tangent), float(lambda0),
-                                float(w_pose), float(w_beta), *(float(v) for v in smooth5), int(free), _stream())
-    return cost, accepted, idx, dist, ws[:32 * S * T].view(torch.float64).reshape(S, T, 4).clone()
+    return _icp_launch(ns.scat_mano_fit_points_seq_ws, ns.scat_mano_fit_points_seq, model, points, weights,
+                       (0, 0, 0) if topo is None else topo.ptrs, p, S, (S, T, N, model.V, 0 if topo is None else topo.F),
+                       (int(rounds), int(iters), float(max_dist), float(w_tangent), float(lambda0), float(w_pose), float(w_beta),
+                        *(float(v) for v in smooth5), int(free)))
 
 
 def mano_fit_seq_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose,
@@ -514,6 +509,30 @@ def mano_fit_seq_kp(model, targets3, weights3, targets2, weights2, joint_map, po
                             float(sigma3), float(sigma2), float(half_w), float(half_h), *(float(v) for v in smooth7), int(free),
                             int(free_cam), _stream())
     return cost, accepted
+
+
+def _icp_front(what, lead, init, w_tangent, rounds, iters, free, max_dist):
+    """What every ICP method checks before it looks at a tensor: the start is required (lead: what the error calls it),
+    w_tangent in [0, 1], iters and free in range, rounds in 1..POINTS_MAX_ROUNDS with at most POINTS_MAX_STEPS steps,
+    max_dist positive or None -> tau, rounds, iters, max_dist as the numbers the launch takes"""
+    if init is None:
+        raise ScatError(f"{what} needs a start: {lead}")
+    tau = float(w_tangent)
+    if not 0.0 <= tau <= 1.0:
+        raise ScatError(f"{what}: w_tangent {w_tangent} outside 0..1")
+    rounds, iters = int(rounds), int(iters)
+    _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+    if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
+        raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
+                        f"{POINTS_MAX_STEPS} steps")
+    return tau, rounds, iters, _max_dist(what, max_dist)
+
+
+def _icp_back(result_type, p, cost, accepted, idx, dist, stats):
+    """the result of an ICP method from what its launch returned: matched and rms from the last assignment's stats"""
+    mw = stats[..., 1]
+    rms = torch.where(mw > 0, (stats[..., 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
+    return result_type(*_groups(p), cost, accepted, p, stats[..., 2].long(), rms, idx, dist)
 
 
 class ManoFitter:
@@ -608,23 +627,14 @@ class ManoFitter:
         a negative weight, is not fitted: data_cost +inf, accepted 0, p the start; a hand with nothing matched keeps its
         p too."""
         what = "ManoFitter.fit_points"
-        if init is None:
-            raise ScatError(f"{what} needs a start: p [B,62] or a fit result")
+        _, rounds, iters, max_dist = _icp_front(what, "p [B,62] or a fit result", init, 1.0, rounds, iters, free, max_dist)
         points, weights = self._cloud(what, points, weights)
         B = points.shape[0]
         if isinstance(init, KeypointFitResult):
             init = init.p[:, :UNKNOWNS]
         p = _start(what, init, (FitResult, PointFitResult), (B, UNKNOWNS), points.device)
-        rounds, iters = int(rounds), int(iters)
-        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
-        if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
-            raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
-                            f"{POINTS_MAX_STEPS} steps")
-        cost, accepted, idx, dist, stats = mano_fit_points(self.model, points, weights, p, rounds, iters, _max_dist(what, max_dist),
-                                                           self.lambda0, self.w_pose, self.w_beta, free)
-        mw = stats[:, 1]
-        rms = torch.where(mw > 0, (stats[:, 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
-        return PointFitResult(*_groups(p), cost, accepted, p, stats[:, 2].long(), rms, idx, dist)
+        return _icp_back(PointFitResult, p, *mano_fit_points(self.model, points, weights, p, rounds, iters, max_dist, self.lambda0,
+                                                            self.w_pose, self.w_beta, free))
 
     def nearest_vertices(self, result_or_verts, points, weights=None, max_dist=None):
         """-> Correspondences of the cloud points [B,N,3] with the model at a fit result or p [B,62] (the vertices are
@@ -705,11 +715,7 @@ class ManoFitter:
         Euclidean, to the nearest vertex.  init, weights, rounds, iters, max_dist, free, the limits and what makes a hand
         unusable are fit_points'.  On a cloud that IS the model's vertices fit_points is the better method."""
         what = "ManoFitter.fit_points_plane"
-        if init is None:
-            raise ScatError(f"{what} needs a start: p [B,62] or a fit result")
-        tau = float(w_tangent)
-        if not 0.0 <= tau <= 1.0:
-            raise ScatError(f"{what}: w_tangent {w_tangent} outside 0..1")
+        tau, rounds, iters, max_dist = _icp_front(what, "p [B,62] or a fit result", init, w_tangent, rounds, iters, free, max_dist)
         self._host_topology(what, faces)
         points, weights = self._cloud(what, points, weights)
         B = points.shape[0]
@@ -717,17 +723,8 @@ class ManoFitter:
         if isinstance(init, KeypointFitResult):
             init = init.p[:, :UNKNOWNS]
         p = _start(what, init, (FitResult, PointFitResult), (B, UNKNOWNS), points.device)
-        rounds, iters = int(rounds), int(iters)
-        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
-        if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
-            raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
-                            f"{POINTS_MAX_STEPS} steps")
-        cost, accepted, idx, dist, stats = mano_fit_points_plane(self.model, points, weights, topo, p, rounds, iters,
-                                                                 _max_dist(what, max_dist), tau, self.lambda0, self.w_pose,
-                                                                 self.w_beta, free)
-        mw = stats[:, 1]
-        rms = torch.where(mw > 0, (stats[:, 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
-        return PointFitResult(*_groups(p), cost, accepted, p, stats[:, 2].long(), rms, idx, dist)
+        return _icp_back(PointFitResult, p, *mano_fit_points_plane(self.model, points, weights, topo, p, rounds, iters, max_dist, tau,
+                                                                  self.lambda0, self.w_pose, self.w_beta, free))
 
     def vertex_normals(self, result_or_verts, faces):
         """-> [B,V,3] fp32, the area-weighted unit vertex normals of the fitted mesh of a result (mesh(result)) or of the
@@ -841,12 +838,9 @@ class ManoFitter:
         data_cost +inf in the frames concerned.  The other sequences are not affected.
         weights, max_dist, free and the limits (rounds in 1..64, rounds x iters <= 256) are fit_points'."""
         what = "ManoFitter.fit_points_sequence"
-        if init is None:
-            raise ScatError(f"{what} needs a start: p [S,T,62] or a sequence fit result")
+        tau, rounds, iters, max_dist = _icp_front(what, "p [S,T,62] or a sequence fit result", init, w_tangent,
+                                                  (10 if faces is not None else 5) if rounds is None else rounds, iters, free, max_dist)
         sm = _smooth(what, smooth)
-        tau = float(w_tangent)
-        if not 0.0 <= tau <= 1.0:
-            raise ScatError(f"{what}: w_tangent {w_tangent} outside 0..1")
         if faces is not None:
             self._host_topology(what, faces)
         _need_gpu(what, points, *(() if weights is None else (weights,)))
@@ -859,17 +853,9 @@ class ManoFitter:
         weights = _weights(what, weights, tuple(points.shape[:3]))
         topo = None if faces is None else self._topology(what, faces, points.device)
         p = self._start_sequence(what, init, S, T, points.device)
-        rounds, iters = int((10 if faces is not None else 5) if rounds is None else rounds), int(iters)
-        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
-        if not 1 <= rounds <= POINTS_MAX_ROUNDS or rounds * iters > POINTS_MAX_STEPS:
-            raise ScatError(f"{what}: {rounds} rounds of {iters} iterations: rounds outside 1..{POINTS_MAX_ROUNDS} or more than "
-                            f"{POINTS_MAX_STEPS} steps")
-        cost, accepted, idx, dist, stats = mano_fit_points_seq(self.model, points.contiguous(), weights, topo, p, rounds, iters,
-                                                               _max_dist(what, max_dist), tau, self.lambda0, self.w_pose,
-                                                               self.w_beta, sm, free)
-        mw = stats[..., 1]
-        rms = torch.where(mw > 0, (stats[..., 3] / mw).sqrt(), torch.full_like(mw, float("inf"))).float()
-        return PointSequenceFitResult(*_groups(p), cost, accepted, p, stats[..., 2].long(), rms, idx, dist)
+        return _icp_back(PointSequenceFitResult, p, *mano_fit_points_seq(self.model, points.contiguous(), weights, topo, p, rounds,
+                                                                        iters, max_dist, tau, self.lambda0, self.w_pose,
+                                                                        self.w_beta, sm, free))
 
     def fit_outputs_sequence(self, out66, weights=None, smooth=None):
         """out66 [S,T,66]: the network's camera and 21 root-relative joints for every frame of S tracks; the joints are

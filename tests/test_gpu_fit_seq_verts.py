@@ -278,6 +278,38 @@ def test_icp_matches_the_oracle(plane):
 
 
 @pytest.mark.parametrize("plane", [False, True])
+def test_fit_points_sequence_is_assign_and_track_solve_composed(plane):
+    """one round at S 2, T 3, V 37, N 64 (the first 64 points of icp_case's frames): the loop is the assignment over the S T
+    frames, scat_mano_fit_seq_verts on its targets, weights and normals, and the assignment again, bit for bit.  Every
+    frame has matched weight: the public solve does not see the assignment's stats, so it would take a frame in which
+    nothing matched, whose weights are a NaN row, for unusable where the loop bridges it"""
+    from scat_amd.fit import mano_cloud_assign_plane, mano_fit_seq_verts
+
+    S, T, V, N, k = 2, 3, 37, 64, 2
+    pts, P0, topo = G.icp_case(S, T)
+    pts = torch.from_numpy(np.ascontiguousarray(np.array(pts)[:, :, :N])).to(DEV)
+    f, q = fitter(V), pts.reshape(S * T, N, 3)
+
+    def assign(p):
+        if not plane:
+            return f.nearest_vertices(p, q, None, G.ICP_TRIM), None
+        return mano_cloud_assign_plane(f.model, p, q, None, f._topology("test", topo[0], q.device), G.ICP_TRIM, G.TAU)
+
+    p = P0.to(DEV).clone()
+    c, n = assign(p.view(S * T, 62))
+    assert bool((c.matched_weight > 0).all()) and bool(torch.isfinite(c.vertex_weight).all())      # the precondition
+    cost, acc = mano_fit_seq_verts(f.model, c.vertex_target.view(S, T, V, 3), c.vertex_weight.view(S, T, V),
+                                   None if n is None else n.view(S, T, V, 3), p, k, 0, G.TAU, f.lambda0, f.w_pose, f.w_beta,
+                                   G.sm(G.ICP_SMOOTH))
+    c = assign(p.view(S * T, 62))[0]
+    r = f.fit_points_sequence(pts, P0.to(DEV), faces=topo[0] if plane else None, smooth=G.ICP_SMOOTH, rounds=1, iters=k,
+                              max_dist=G.ICP_TRIM, w_tangent=G.TAU)
+    assert bool((acc > 0).all()) and not torch.equal(p, P0.to(DEV))
+    assert same_bits((r.p, r.accepted, r.idx, r.dist, r.data_cost),
+                     (p, acc, c.idx.view(S, T, N), c.dist.view(S, T, N), c.data_cost.float().view(S, T)))
+
+
+@pytest.mark.parametrize("plane", [False, True])
 def test_icp_bridges_a_frame_where_nothing_matches(plane):
     pts, P0, topo = G.icp_case(2, 3, 1)
     Po, acc, dc, a, margin = G.icp_run(2, 3, plane, 1)

@@ -5,9 +5,10 @@ compare against (SCAT_LIBPATH) and once with this tree's, each in its own proces
 (profiles/fit_family_refactor.txt is such a pair).
 
 The smallest shapes: V = 37, and 778 once per entry point; 6 hands for the joints, keypoint and mesh fits, 2 sequences of 5
-frames (joints and keypoints; at V = 37 also of 1 and of 2 frames, the block-tridiagonal walk's smallest), a cloud of
-(3, 257, 37).  5 iterations; the closed-form start and the caller's; one run with a frozen group and one with some zero
-weights."""
+frames (joints, keypoints, meshes and clouds; at V = 37 also of 1 and of 2 frames, the block-tridiagonal walk's smallest), a
+cloud of (3, 257, 37).  5 iterations; the closed-form start and the caller's; one run with a frozen group and one with some
+zero weights.  The plane metric (the mesh fit at three tau, the normals, the assignment, the loop) and the tracks of meshes
+and clouds (a frame without weight, a frame in which nothing matches) come last per V."""
 import hashlib
 import os
 import sys
@@ -24,14 +25,17 @@ ITERS = 5
 
 def main():
     import _fit_kp_cases as KC
+    import _fit_plane_cases as LC
     import _fit_points_cases as PC
     import _fit_seq_cases as SC
     import _fit_seq_kp_cases as QC
+    import _fit_seq_verts_cases as GC
     import _fit_verts_cases as VC
     from _fit_cases import JOINT_MAP, host_model
     from scat_amd import synth
     from scat_amd._lib import lib
-    from scat_amd.fit import ManoFitter, free_mask, mano_joints_jac, mano_verts_jac
+    from scat_amd.fit import (ManoFitter, Topology, free_mask, mano_cloud_assign_plane, mano_fit_verts_metric, mano_joints_jac,
+                              mano_verts_jac, mesh_normals)
 
     lib().scat_check_device()
     dev = torch.device("cuda", 0)
@@ -127,6 +131,46 @@ def main():
         show(f"v{V}.points", fitter.fit_points(points, start, rounds=3, iters=ITERS))
         show(f"v{V}.points.trim", fitter.fit_points(points, start, weights=weights, rounds=3, iters=ITERS, max_dist=max_dist))
         show(f"v{V}.points.frozen", fitter.fit_points(points, start, weights=weights, rounds=2, iters=ITERS, free=frozen))
+
+        # the plane metric: the mesh fit on _fit_plane_cases.metric_case, then the cloud above against topology(V)
+        Mv, mw, mn, M1 = (t.float().to(dev) for t in LC.metric_case(V))
+        for tau in LC.TAUS:
+            mp = M1.clone()
+            show(f"v{V}.metric.tau{tau:g}", (mp, *mano_fit_verts_metric(fitter.model, Mv, mw, mn, mp, ITERS, tau, fitter.lambda0,
+                                                                        fitter.w_pose, fitter.w_beta)))
+        faces = LC.topology(V)[0]
+        topo = Topology(*(torch.from_numpy(np.array(a)).to(dev) for a in LC.topology(V)))
+        show(f"v{V}.normals", (mesh_normals(Tv, topo),))
+        ca, cn, cm = mano_cloud_assign_plane(fitter.model, start, points, weights, topo, max_dist, LC.TAU, want_model_pts=True)
+        show(f"v{V}.assign_plane", ca)
+        show(f"v{V}.assign_plane.more", (cn, cm))
+        show(f"v{V}.plane", fitter.fit_points_plane(points, start, faces, rounds=3, iters=ITERS))
+        show(f"v{V}.plane.trim", fitter.fit_points_plane(points, start, faces, weights=weights, rounds=3, iters=ITERS, max_dist=max_dist))
+        show(f"v{V}.plane.frozen", fitter.fit_points_plane(points, start, faces, weights=weights, rounds=2, iters=ITERS, free=frozen))
+
+        # tracks of meshes: _fit_seq_verts_cases.track at S 2 T 5, a start 0.05 off, a frame without weight
+        Pv, Xv = GC.track(25, 2, 5, V)
+        Xv, near_v = Xv.to(dev), GC.off_start(Pv, 23).float().to(dev)
+        wx = torch.ones(2, 5, V, device=dev)
+        wx[:, 2] = 0.0
+        wx[:, :, ::3] = 0.0
+        seqv = fitter.fit_vertices_sequence
+        show(f"v{V}.seqv", seqv(Xv, smooth=GC.SMOOTH))
+        show(f"v{V}.seqv.init", seqv(Xv, smooth=GC.SMOOTH, init=near_v))
+        show(f"v{V}.seqv.frozen", seqv(Xv, smooth=GC.SMOOTH, init=near_v, free=frozen))
+        show(f"v{V}.seqv.weights", seqv(Xv, weights=wx, smooth=GC.SMOOTH))
+        if V == 37:
+            for T in (1, 2):
+                show(f"v{V}.seqv.t{T}", seqv(GC.track(25, 2, T, V)[1].to(dev), smooth=GC.SMOOTH))
+        # tracks of clouds: 257 points 3 mm off the meshes' vertices; in the last, frame 2 of sequence 0 sits 1 m away
+        sn = torch.from_numpy(np.array(synth.normal_like(31, "bits.seq.noise", (2, 5, 257, 3), 0.003))).float().to(dev)
+        cloud_s = (Xv[:, :, torch.arange(257, device=dev) * 7 % V] + sn).contiguous()
+        gap = cloud_s.clone()
+        gap[0, 2] += 1.0
+        seqp = fitter.fit_points_sequence
+        show(f"v{V}.seqp", seqp(cloud_s, near_v, smooth=GC.ICP_SMOOTH, rounds=2, iters=ITERS))
+        show(f"v{V}.seqp.plane", seqp(cloud_s, near_v, faces=faces, smooth=GC.ICP_SMOOTH, rounds=2, iters=ITERS))
+        show(f"v{V}.seqp.gap", seqp(gap, near_v, faces=faces, smooth=GC.ICP_SMOOTH, rounds=2, iters=ITERS, max_dist=GC.ICP_TRIM))
     torch.cuda.synchronize()
 
 
