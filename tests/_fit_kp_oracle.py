@@ -1,6 +1,6 @@
 """fp64 torch statement of the MANO fit to keypoints of include/scat_mano_fit_kp.h on top of _fit_oracle.joints: the 3-D
 model joints and their weak-perspective projection, the robust cost with priors and limits, the IRLS normal equations
-(Jacobian of all 105 residual rows by torch.autograd.functional.jacobian), both closed-form starts and the
+(Jacobian of all 105 residual rows by torch.autograd.functional.jacobian), both closed-form starts and _lm_oracle's
 Levenberg-Marquardt loop with the kernel's rules.  Test-only: imports none of scat_amd's kernels.
 
 Everything takes a dtype, as _fit_oracle does: the fp32 run exists only to measure what fp32 rounding does to a result (the
@@ -12,10 +12,12 @@ import numpy as np
 import torch
 
 import _fit_oracle as FO
+import _lm_oracle as L
 import _mano_oracle as MO
 
 U, U3 = 65, 62
 LAMBDA_MIN, LAMBDA_MAX = FO.LAMBDA_MIN, FO.LAMBDA_MAX
+model_joints, rel = FO.model_joints, MO.rel
 
 
 class Problem(NamedTuple):
@@ -48,10 +50,6 @@ def project(P, m3, half):
     """u = (cs (m.x + ctx) half_w + half_w, cs (m.y + cty) half_h + half_h), [B,21,2]"""
     h = torch.tensor(half, dtype=P.dtype)
     return (P[:, 62].reshape(-1, 1, 1) * (m3[:, :, :2] + P[:, None, 63:65])) * h + h
-
-
-def model_joints(model, P, joint_map):
-    return FO.model_joints(model, P, joint_map)
 
 
 def reproject(model, P, joint_map, half):
@@ -113,47 +111,18 @@ def normal_equations(model, P, pr, free=(1 << U3) - 1, free_cam=7):
         e3, e2 = (r[:, :63].reshape(B, 21, 3) ** 2).sum(2), (r[:, 63:].reshape(B, 21, 2) ** 2).sum(2)
         wr = torch.cat([(w3 * rho_prime(e3, pr.sigma3)).repeat_interleave(3, dim=1),
                         (w2 * rho_prime(e2, pr.sigma2)).repeat_interleave(2, dim=1)], dim=1)
-        prior = torch.zeros(U, dtype=dt)
-        prior[3:48], prior[48:58] = pr.w_pose, pr.w_beta
         ex = excess(P, pr)
         lim_d, lim_g = torch.zeros(B, U, dtype=dt), torch.zeros(B, U, dtype=dt)
         lim_d[:, 3:48], lim_g[:, 3:48] = pr.w_limit * (ex != 0).to(dt), pr.w_limit * ex
-        A = J.transpose(1, 2) @ (wr.unsqueeze(2) * J) + torch.diag(prior) + torch.diag_embed(lim_d)
-        g = (J.transpose(1, 2) @ (wr * r).unsqueeze(2)).squeeze(2) + prior * P + lim_g
-        fr = torch.tensor(free_bits(free, free_cam), dtype=torch.bool)
-        keep = (fr[:, None] & fr[None, :]).to(dt)
-        A = A * keep + torch.diag((~fr).to(dt))
-    return A, g * fr.to(dt)
+        A, g = L.gauss_newton(J, wr, r, FO.prior_vec(U, dt, pr.w_pose, pr.w_beta), P)
+        return L.freeze(A + torch.diag_embed(lim_d), g + lim_g, torch.tensor(free_bits(free, free_cam)))
 
 
 def lm(model, pr, P0, iters, lambda0=1e-3, free=(1 << U3) - 1, free_cam=7, history=False):
-    """-> P [B,65], cost [B], accepted [B] (and the per-iteration costs [iters,B] and iterates [iters,B,65]) in P0's dtype"""
-    dt = P0.dtype
-    P = P0.clone()
-    B = P.shape[0]
-    lam = torch.full((B,), lambda0, dtype=dt)
-    acc = torch.zeros(B, dtype=torch.int32)
-    fr = torch.tensor(free_bits(free, free_cam), dtype=dt)
-    hist, trace, c = [], [], None
-    for _ in range(iters):
-        A, g = normal_equations(model, P, pr, free, free_cam)
-        with torch.no_grad():
-            c = cost(model, P, pr)
-            Ad = A + lam.reshape(B, 1, 1) * torch.diag_embed(torch.diagonal(A, dim1=1, dim2=2))
-            L, info = torch.linalg.cholesky_ex(Ad)
-            ok = (info == 0) & torch.isfinite(L).all(2).all(1)
-            L = torch.where(ok.reshape(B, 1, 1), L, torch.eye(U, dtype=dt).expand(B, U, U))
-            delta = -torch.cholesky_solve(g.unsqueeze(2), L).squeeze(2) * fr
-            Pt = P + delta
-            ct = cost(model, Pt, pr)
-            take = ok & torch.isfinite(Pt).all(1) & (ct < c)
-            P = torch.where(take.unsqueeze(1), Pt, P)
-            c = torch.where(take, ct, c)
-            acc += take.to(torch.int32)
-            lam = torch.where(take, (lam * 0.1).clamp_min(LAMBDA_MIN), (lam * 10).clamp_max(LAMBDA_MAX))
-            hist.append(c.clone())
-            trace.append(P.clone())
-    return (P, c, acc, torch.stack(hist), torch.stack(trace)) if history else (P, c, acc)
+    """-> P [B,65], cost [B], accepted [B] (and the per-iteration costs [iters,B] and iterates [iters,B,65]) in P0's
+    dtype: _lm_oracle.lm, which here also rejects a factor that is not finite and runs without gradients throughout"""
+    return L.lm(P0, iters, lambda0, lambda P: normal_equations(model, P, pr, free, free_cam), lambda P: cost(model, P, pr),
+                torch.tensor(free_bits(free, free_cam), dtype=P0.dtype), finite_factor=True, no_grad=True)[:5 if history else 3]
 
 
 def _procrustes(X, T, w):
@@ -236,7 +205,3 @@ def rms2(model, P, T2, joint_map, half, sel=None):
     if sel is None:
         return d.mean(1).sqrt()
     return ((d * sel).sum(1) / sel.sum(1)).sqrt()
-
-
-def rel(a, b):
-    return MO.rel(a, b)

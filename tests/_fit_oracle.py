@@ -1,7 +1,7 @@
 """fp64 torch statement of the MANO fit of include/scat_mano_fit.h on top of _mano_oracle.forward: the model joints, the
-cost, the Jacobian (torch.autograd.functional.jacobian), the Procrustes start and the Levenberg-Marquardt loop with the
-kernel's rules (Marquardt scaling, accept only if the cost drops, lambda / 10 or x 10 within 1e-12..1e12, a failed
-Cholesky is a rejection, frozen unknowns are unit rows).  Test-only: imports none of scat_amd's kernels.
+cost, the Jacobian (torch.autograd.functional.jacobian) and the normal equations; the Procrustes start and the
+Levenberg-Marquardt loop with the kernel's rules are _lm_oracle's, which every fit oracle shares.  Test-only: imports
+none of scat_amd's kernels.
 
 Everything takes a dtype.  In fp64 the joints are _mano_oracle.forward's; in fp32 they come from joints_any below, the
 same formulas in the tensors' own dtype, which exists only to measure what fp32 rounding does to a result: the GPU gates
@@ -10,10 +10,12 @@ _mano_oracle.forward in fp64)."""
 import numpy as np
 import torch
 
+import _lm_oracle as L
 import _mano_oracle as MO
 
 U, NM = 62, 58
-LAMBDA_MIN, LAMBDA_MAX = 1e-12, 1e12
+LAMBDA_MIN, LAMBDA_MAX = L.LAMBDA_MIN, L.LAMBDA_MAX
+rel, rot_to_axis_angle = MO.rel, L.rot_to_axis_angle
 
 
 def rodrigues_any(r):
@@ -35,20 +37,21 @@ def rodrigues_any(r):
     return eye + a.reshape(-1, 1, 1) * S + b.reshape(-1, 1, 1) * S2
 
 
-def joints_any(model, rots, poses, betas):
-    """the first 21 rows of _mano_oracle.forward in the inputs' dtype; the model's fp32 arrays are exact in either"""
+def skinned_any(model, rots, poses, betas, rows):
+    """what joints_any and _fit_verts_oracle.verts_any share, in the inputs' dtype (the model's fp32 arrays are exact in either):
+    the chain joints t [B,16,3] and the skinned vertices v of rows (a list, or slice(None): all) before the global rotation"""
     dt = rots.dtype
     T = lambda a: torch.from_numpy(np.asarray(a)).to(dt)
     vt, sd, pd = T(model.v_template), T(model.shapedirs), T(model.posedirs)
     Jr, W, hm = T(model.J_regressor), T(model.weights), T(model.hands_mean)
-    parents, tips = list(model.parents), list(model.tips)
+    parents = list(model.parents)
     B = rots.shape[0]
     pose = torch.cat([torch.zeros(B, 1, 3, dtype=dt), (hm.reshape(1, 45) + poses).reshape(B, 15, 3)], dim=1)
     R = rodrigues_any(pose.reshape(-1, 3)).reshape(B, 16, 3, 3)
     v_shaped = vt.unsqueeze(0) + torch.einsum("vck,bk->bvc", sd, betas)
     J = torch.einsum("jv,bvc->bjc", Jr, v_shaped)
     pw = (R[:, 1:] - torch.eye(3, dtype=dt)).reshape(B, 135)
-    vp = v_shaped[:, tips] + torch.einsum("vck,bk->bvc", pd[tips], pw)
+    vp = v_shaped[:, rows] + torch.einsum("vck,bk->bvc", pd[rows], pw)
     RG, t = [R[:, 0]], [J[:, 0]]
     for i in range(1, 16):
         p = parents[i]
@@ -56,9 +59,14 @@ def joints_any(model, rots, poses, betas):
         t.append((RG[p] @ (J[:, i] - J[:, p]).unsqueeze(2)).squeeze(2) + t[p])
     RG, t = torch.stack(RG, 1), torch.stack(t, 1)
     a = t - (RG @ J.unsqueeze(3)).squeeze(3)
-    TR = torch.einsum("vi,birc->bvrc", W[tips], RG)
-    Ta = torch.einsum("vi,bir->bvr", W[tips], a)
-    v = (TR @ vp.unsqueeze(3)).squeeze(3) + Ta
+    TR = torch.einsum("vi,birc->bvrc", W[rows], RG)
+    Ta = torch.einsum("vi,bir->bvr", W[rows], a)
+    return t, (TR @ vp.unsqueeze(3)).squeeze(3) + Ta
+
+
+def joints_any(model, rots, poses, betas):
+    """the first 21 rows of _mano_oracle.forward in the inputs' dtype: rotated as one array, then joint 1 subtracted"""
+    t, v = skinned_any(model, rots, poses, betas, list(model.tips))
     x = torch.cat([t, v], dim=1) @ rodrigues_any(rots).transpose(1, 2)
     return x - x[:, 1:2]
 
@@ -98,105 +106,60 @@ def rms(model, P, targets, joint_map):
     return (d * d).sum(2).mean(1).sqrt()
 
 
-def rot_to_axis_angle(R):
-    """[B,3,3] -> [B,3] through the unit quaternion with w >= 0: 2 atan2(|v|, w) v / |v|, accurate at 0 and at pi"""
-    out = []
-    for M in R.double().numpy():
-        tr = M[0, 0] + M[1, 1] + M[2, 2]
-        if tr > 0:
-            S = 2 * np.sqrt(tr + 1)
-            q = [S / 4, (M[2, 1] - M[1, 2]) / S, (M[0, 2] - M[2, 0]) / S, (M[1, 0] - M[0, 1]) / S]
-        elif M[0, 0] > M[1, 1] and M[0, 0] > M[2, 2]:
-            S = 2 * np.sqrt(1 + M[0, 0] - M[1, 1] - M[2, 2])
-            q = [(M[2, 1] - M[1, 2]) / S, S / 4, (M[0, 1] + M[1, 0]) / S, (M[0, 2] + M[2, 0]) / S]
-        elif M[1, 1] > M[2, 2]:
-            S = 2 * np.sqrt(1 + M[1, 1] - M[0, 0] - M[2, 2])
-            q = [(M[0, 2] - M[2, 0]) / S, (M[0, 1] + M[1, 0]) / S, S / 4, (M[1, 2] + M[2, 1]) / S]
-        else:
-            S = 2 * np.sqrt(1 + M[2, 2] - M[0, 0] - M[1, 1])
-            q = [(M[1, 0] - M[0, 1]) / S, (M[0, 2] + M[2, 0]) / S, (M[1, 2] + M[2, 1]) / S, S / 4]
-        q = np.array(q) * (1.0 if q[0] >= 0 else -1.0)
-        n = np.linalg.norm(q[1:])
-        out.append(q[1:] * (2 * np.arctan2(n, q[0]) / n if n > 1e-12 else 2.0))
-    return torch.tensor(np.array(out), dtype=torch.float64)
-
-
-def procrustes_start(model, targets, w, joint_map):
-    """init = 1: zeros for pose and shape, the weighted similarity Procrustes (SVD form) of the zero-pose joints onto the
-    targets for rots, trans, log_scale.  fp64 whatever the targets' dtype, as in the kernel."""
-    T, w = targets.double(), w.double()
-    B = T.shape[0]
-    P = torch.zeros(B, U, dtype=torch.float64)
-    X = joints(model, P)[:, list(joint_map)]
-    W = w.sum(1).reshape(B, 1)
-    mx, my = (w.unsqueeze(2) * X).sum(1) / W, (w.unsqueeze(2) * T).sum(1) / W
-    Xc, Tc = X - mx.unsqueeze(1), T - my.unsqueeze(1)
-    K = torch.einsum("bj,bja,bjc->bac", w, Xc, Tc)           # sum_j w x y^T
-    Uu, S, Vh = torch.linalg.svd(K)
-    d = torch.sign(torch.linalg.det(Vh.transpose(1, 2) @ Uu.transpose(1, 2)))
-    D = torch.diag_embed(torch.stack([torch.ones_like(d), torch.ones_like(d), d], 1))
-    R = Vh.transpose(1, 2) @ D @ Uu.transpose(1, 2)          # y ~ R x
-    var = (w * (Xc * Xc).sum(2)).sum(1)
-    sc = torch.einsum("bca,bac->b", R, K) / var
-    P[:, 0:3] = rot_to_axis_angle(R)
-    P[:, 58:61] = my - sc.reshape(B, 1) * (R @ mx.unsqueeze(2)).squeeze(2)
-    P[:, 61] = torch.log(sc)
+def similarity_start(X, targets, w):
+    """zeros for pose and shape [B,62] fp64; rots, trans, log_scale: the weighted similarity Procrustes of X onto the targets"""
+    P = torch.zeros(targets.shape[0], U, dtype=torch.float64)
+    P[:, 0:3], P[:, 58:61], P[:, 61] = L.procrustes(X, targets, w)
     return P
 
 
+def procrustes_start(model, targets, w, joint_map):
+    """init = 1: similarity_start of the zero-pose joints, computed in fp64; fp64 whatever the targets' dtype, as in the kernel"""
+    X = joints(model, torch.zeros(targets.shape[0], U, dtype=torch.float64))[:, list(joint_map)]
+    return similarity_start(X, targets.double(), w.double())
+
+
+def prior_vec(n, dt, w_pose, w_beta):
+    """the n priors' weights: w_pose on the 45 poses, w_beta on the 10 betas"""
+    return L.group_vec(((3, 0.0), (45, w_pose), (10, w_beta), (n - NM, 0.0)), dt)
+
+
+def rows(x, jm, P, targets):
+    """the model's points x [B,K,3] and their Jacobian jm [B,3K,58] -> the rows Jf [B,K,3,62] and residuals r [B,K,3] of
+    exp(log_scale) x + trans - targets (targets 0.0: the scaled and moved points themselves)"""
+    B, K, dt = x.shape[0], x.shape[1], P.dtype
+    s = torch.exp(P[:, 61]).reshape(B, 1, 1)
+    Jf = torch.zeros(B, 3 * K, U, dtype=dt)
+    Jf[:, :, :NM] = s * jm
+    Jf[:, :, 58:61] = torch.eye(3, dtype=dt).repeat(K, 1).unsqueeze(0)
+    Jf[:, :, 61] = (s * x).reshape(B, 3 * K)
+    return Jf.reshape(B, K, 3, U), s * x + P[:, None, 58:61] - targets
+
+
+def row_equations(Jf, r, w, P, w_pose, w_beta, free):
+    """rows' Jf, r and the points' weights w [B,K] -> A [B,62,62] (undamped), g [B,62], cost [B] at P: the Gauss-Newton
+    product with the priors, the frozen unknowns as unit rows with g = 0"""
+    B = P.shape[0]
+    Jf, r, wr = Jf.reshape(B, -1, U), r.reshape(B, -1), w.repeat_interleave(3, dim=1)
+    A, g = L.gauss_newton(Jf, wr, r, prior_vec(U, P.dtype, w_pose, w_beta), P)
+    c = (wr * r * r).sum(1) + w_pose * (P[:, 3:48] ** 2).sum(1) + w_beta * (P[:, 48:58] ** 2).sum(1)
+    return L.freeze(A, g, L.mask_vec(free, U, P.dtype)) + (c,)
+
+
 def normal_equations(model, P, targets, w, joint_map, w_pose, w_beta, free):
-    """-> A [B,62,62] (undamped), g [B,62], cost [B] at P, the frozen unknowns as unit rows with g = 0"""
-    B, dt = P.shape[0], P.dtype
+    """-> A [B,62,62] (undamped), g [B,62], cost [B] at P: row_equations of the mapped joints"""
     x, jm = joints_jac(model, P)
     jmap = list(joint_map)
-    s = torch.exp(P[:, 61]).reshape(B, 1, 1)
-    xm = x[:, jmap]
-    Jf = torch.zeros(B, 63, U, dtype=dt)
-    Jf[:, :, :NM] = s * jm.reshape(B, 21, 3, NM)[:, jmap].reshape(B, 63, NM)
-    Jf[:, :, 58:61] = torch.eye(3, dtype=dt).repeat(21, 1).unsqueeze(0)
-    Jf[:, :, 61] = (s * xm).reshape(B, 63)
-    r = (s * xm + P[:, None, 58:61] - targets).reshape(B, 63)
-    wr = w.repeat_interleave(3, dim=1)
-    prior = torch.zeros(U, dtype=dt)
-    prior[3:48], prior[48:58] = w_pose, w_beta
-    A = Jf.transpose(1, 2) @ (wr.unsqueeze(2) * Jf) + torch.diag(prior)
-    g = (Jf.transpose(1, 2) @ (wr * r).unsqueeze(2)).squeeze(2) + prior * P
-    c = (wr * r * r).sum(1) + w_pose * (P[:, 3:48] ** 2).sum(1) + w_beta * (P[:, 48:58] ** 2).sum(1)
-    fr = torch.tensor([(free >> i) & 1 for i in range(U)], dtype=torch.bool)
-    keep = (fr[:, None] & fr[None, :]).to(dt)
-    A = A * keep + torch.diag((~fr).to(dt))
-    return A, g * fr.to(dt), c
+    Jf, r = rows(x[:, jmap], jm.reshape(-1, 21, 3, NM)[:, jmap].reshape(-1, 63, NM), P, targets)
+    return row_equations(Jf, r, w, P, w_pose, w_beta, free)
 
 
 def lm(model, targets, w, joint_map, P0, iters, lambda0=1e-3, w_pose=1e-6, w_beta=1e-6, free=(1 << U) - 1, history=False):
-    """-> P [B,62], cost [B], accepted [B] (and the per-iteration costs [iters,B]) in P0's dtype"""
+    """-> P [B,62], cost [B], accepted [B] (and the per-iteration costs [iters,B]) in P0's dtype: _lm_oracle.lm"""
     dt = P0.dtype
     targets, w = targets.to(dt), w.to(dt)
-    P = P0.clone()
-    B = P.shape[0]
-    lam = torch.full((B,), lambda0, dtype=dt)
-    acc = torch.zeros(B, dtype=torch.int32)
-    fr = torch.tensor([(free >> i) & 1 for i in range(U)], dtype=dt)
-    hist, c = [], None
-    for _ in range(iters):
-        A, g, _ = normal_equations(model, P, targets, w, joint_map, w_pose, w_beta, free)
-        with torch.no_grad():      # by the same expression as the trial's, so that a rejected step leaves the same bits
-            c = cost(model, P, targets, w, joint_map, w_pose, w_beta)
-        Ad = A + lam.reshape(B, 1, 1) * torch.diag_embed(torch.diagonal(A, dim1=1, dim2=2))
-        L, info = torch.linalg.cholesky_ex(Ad)
-        ok = info == 0
-        L = torch.where(ok.reshape(B, 1, 1), L, torch.eye(U, dtype=dt).expand(B, U, U))
-        delta = -torch.cholesky_solve(g.unsqueeze(2), L).squeeze(2) * fr
-        Pt = P + delta
-        with torch.no_grad():
-            ct = cost(model, Pt, targets, w, joint_map, w_pose, w_beta)
-        take = ok & torch.isfinite(Pt).all(1) & (ct < c)
-        P = torch.where(take.unsqueeze(1), Pt, P)
-        c = torch.where(take, ct, c)
-        acc += take.to(torch.int32)
-        lam = torch.where(take, (lam * 0.1).clamp_min(LAMBDA_MIN), (lam * 10).clamp_max(LAMBDA_MAX))
-        hist.append(c.clone())
-    return (P, c, acc, torch.stack(hist)) if history else (P, c, acc)
+    return L.lm(P0, iters, lambda0, lambda P: normal_equations(model, P, targets, w, joint_map, w_pose, w_beta, free)[:2],
+                lambda P: cost(model, P, targets, w, joint_map, w_pose, w_beta), L.mask_vec(free, U, dt))[:4 if history else 3]
 
 
 def seeded_case(seed, B, model, joint_map):
@@ -211,7 +174,3 @@ def seeded_case(seed, B, model, joint_map):
     with torch.no_grad():
         T = model_joints(model, P, joint_map).float()
     return P, T
-
-
-def rel(a, b):
-    return MO.rel(a, b)

@@ -11,11 +11,12 @@ rounding does to a result."""
 import numpy as np
 import torch
 
+import _fit_oracle as FO
 import _fit_points_oracle as PO
 import _fit_verts_oracle as VO
+import _lm_oracle as L
 
-U, NM = VO.U, VO.NM
-LAMBDA_MIN, LAMBDA_MAX = VO.LAMBDA_MIN, VO.LAMBDA_MAX
+U = VO.U
 
 
 def normals(verts, faces, vf_off, vf_idx, round32=False):
@@ -100,19 +101,6 @@ def rho(r, n, tau):
     return torch.where(flat(n), r2, tau * r2 + (1.0 - tau) * nr * nr)
 
 
-def rows(model, P, targets):
-    """the Jacobian rows Jf [B,V,3,62] and residuals r [B,V,3] of _fit_verts_oracle.normal_equations"""
-    B, dt = P.shape[0], P.dtype
-    x, jm = VO.verts_jac(model, P)
-    V = x.shape[1]
-    s = torch.exp(P[:, 61]).reshape(B, 1, 1)
-    Jf = torch.zeros(B, 3 * V, U, dtype=dt)
-    Jf[:, :, :NM] = s * jm
-    Jf[:, :, 58:61] = torch.eye(3, dtype=dt).repeat(V, 1).unsqueeze(0)
-    Jf[:, :, 61] = (s * x).reshape(B, 3 * V)
-    return Jf.reshape(B, V, 3, U), s * x + P[:, None, 58:61] - targets
-
-
 def priors(P, w_pose, w_beta):
     return w_pose * (P[:, 3:48] ** 2).sum(1) + w_beta * (P[:, 48:58] ** 2).sum(1)
 
@@ -124,52 +112,20 @@ def cost(model, P, targets, w, n, tau, w_pose, w_beta):
 def normal_equations(model, P, targets, w, n, tau, w_pose, w_beta, free):
     """-> A [B,62,62] (undamped), g [B,62], cost [B] at P: the weighted rows of every vertex through sqrt(M_v), the frozen
     unknowns as unit rows with g = 0"""
-    B, dt = P.shape[0], P.dtype
-    Jf, r = rows(model, P, targets)
+    B = P.shape[0]
+    Jf, r = VO.rows(model, P, targets)
     S = sqrt_metric(n, tau)
-    Jt, rt = S @ Jf, (S @ r.unsqueeze(-1)).squeeze(-1)
-    V = r.shape[1]
-    Jt, rt, wr = Jt.reshape(B, 3 * V, U), rt.reshape(B, 3 * V), w.repeat_interleave(3, dim=1)
-    prior = torch.zeros(U, dtype=dt)
-    prior[3:48], prior[48:58] = w_pose, w_beta
-    A = Jt.transpose(1, 2) @ (wr.unsqueeze(2) * Jt) + torch.diag(prior)
-    g = (Jt.transpose(1, 2) @ (wr * rt).unsqueeze(2)).squeeze(2) + prior * P
-    c = (w * rho(r, n, tau)).sum(1) + priors(P, w_pose, w_beta)
-    fr = torch.tensor([(free >> i) & 1 for i in range(U)], dtype=torch.bool)
-    keep = (fr[:, None] & fr[None, :]).to(dt)
-    return A * keep + torch.diag((~fr).to(dt)), g * fr.to(dt), c
+    Jt, rt = (S @ Jf).reshape(B, -1, U), (S @ r.unsqueeze(-1)).squeeze(-1).reshape(B, -1)
+    A, g = L.gauss_newton(Jt, w.repeat_interleave(3, dim=1), rt, FO.prior_vec(U, P.dtype, w_pose, w_beta), P)
+    return L.freeze(A, g, L.mask_vec(free, U, P.dtype)) + ((w * rho(r, n, tau)).sum(1) + priors(P, w_pose, w_beta),)
 
 
 def lm(model, targets, w, n, tau, P0, iters, lambda0=1e-3, w_pose=1e-6, w_beta=1e-6, free=(1 << U) - 1, history=False):
-    """-> P [B,62], cost [B], accepted [B] (and the per-iteration costs [iters,B]) in P0's dtype: _fit_verts_oracle.lm with
-    the metric's normal equations and cost"""
+    """-> P [B,62], cost [B], accepted [B] (and the per-iteration costs [iters,B]) in P0's dtype: _lm_oracle.lm"""
     dt = P0.dtype
     targets, w, n = targets.to(dt), w.to(dt), n.to(dt)
-    P = P0.clone()
-    B = P.shape[0]
-    lam = torch.full((B,), lambda0, dtype=dt)
-    acc = torch.zeros(B, dtype=torch.int32)
-    fr = torch.tensor([(free >> i) & 1 for i in range(U)], dtype=dt)
-    hist, c = [], None
-    for _ in range(iters):
-        A, g, _ = normal_equations(model, P, targets, w, n, tau, w_pose, w_beta, free)
-        with torch.no_grad():      # by the same expression as the trial's, so that a rejected step leaves the same bits
-            c = cost(model, P, targets, w, n, tau, w_pose, w_beta)
-        Ad = A + lam.reshape(B, 1, 1) * torch.diag_embed(torch.diagonal(A, dim1=1, dim2=2))
-        L, info = torch.linalg.cholesky_ex(Ad)
-        ok = info == 0
-        L = torch.where(ok.reshape(B, 1, 1), L, torch.eye(U, dtype=dt).expand(B, U, U))
-        delta = -torch.cholesky_solve(g.unsqueeze(2), L).squeeze(2) * fr
-        Pt = P + delta
-        with torch.no_grad():
-            ct = cost(model, Pt, targets, w, n, tau, w_pose, w_beta)
-        take = ok & torch.isfinite(Pt).all(1) & (ct < c)
-        P = torch.where(take.unsqueeze(1), Pt, P)
-        c = torch.where(take, ct, c)
-        acc += take.to(torch.int32)
-        lam = torch.where(take, (lam * 0.1).clamp_min(LAMBDA_MIN), (lam * 10).clamp_max(LAMBDA_MAX))
-        hist.append(c.clone())
-    return (P, c, acc, torch.stack(hist)) if history else (P, c, acc)
+    return L.lm(P0, iters, lambda0, lambda P: normal_equations(model, P, targets, w, n, tau, w_pose, w_beta, free)[:2],
+                lambda P: cost(model, P, targets, w, n, tau, w_pose, w_beta), L.mask_vec(free, U, dt))[:4 if history else 3]
 
 
 def assign_cost(verts, points, weights, idx, matched, n, tau):
@@ -199,40 +155,21 @@ def icp(model, points, weights, P0, topo, rounds, iters, tau, max_dist=np.inf, l
     returned P) and that last assignment; with history also the P of every assignment.  A round: _fit_points_oracle.assign
     at P's model points (fp64), their normals for topo = (faces, vf_off, vf_idx), then lm above on (vtarget, vw, normals);
     a hand with a NaN vw row keeps its P"""
-    P = P0.double().clone()
-    B = P.shape[0]
-    acc, costs, Ps = torch.zeros(B, dtype=torch.int32), [], []
-    for r in range(rounds + 1):
-        Ps.append(P.clone())
-        with torch.no_grad():
-            x = VO.model_verts(model, P).numpy()
-        a = PO.assign(x, points, weights, max_dist)
-        n = normals(x, *topo)
-        bad = a["stats"][:, 0] != 0
-        costs.append(np.where(bad, np.inf, assign_cost(x, points, weights, a["idx"], a["matched"], n, tau)))
-        if r == rounds:
-            break
-        ok = torch.from_numpy(np.isfinite(a["vw"]).all(1))
-        vw = torch.from_numpy(np.where(np.isfinite(a["vw"]), a["vw"], 0.0))
-        Pn, _, an = lm(model, torch.from_numpy(a["vtarget"]), vw, torch.from_numpy(n), tau, P, iters, lambda0, w_pose, w_beta, free)
-        P = torch.where(ok.unsqueeze(1), Pn, P)
-        acc += torch.where(ok, an, torch.zeros_like(an))
-    return (P, acc, np.stack(costs), a) + ((torch.stack(Ps),) if history else ())
+    return PO.icp_loop(model, points, weights, P0, rounds, max_dist, history,
+                       lambda vt, vw, n, P: lm(model, vt, vw, torch.from_numpy(n), tau, P, iters, lambda0, w_pose, w_beta, free),
+                       lambda x: normals(x, *topo),
+                       lambda x, a, n: assign_cost(x, points, weights, a["idx"], a["matched"], n, tau))
 
 
 def point_normal_equations(model, P, points, weights, idx, matched, n, tau, w_pose, w_beta):
     """the Gauss-Newton system of sum_n w_n r_n^T M_c(n) r_n + priors with one row triple per matched point (rows J_c(n),
     residual model_c(n) - q_n, the metric M itself between them) -> A [B,62,62], g [B,62], cost [B]: what the per-vertex
     form with sqrt(M) on its rows must reproduce"""
-    B, dt = P.shape[0], P.dtype
-    with torch.no_grad():
-        mv = VO.model_verts(model, P)
-    Jf, _ = rows(model, P, mv)
+    Jf, mv = VO.rows(model, P, 0.0)
     M = metric(n, tau)
-    prior = torch.zeros(U, dtype=dt)
-    prior[3:48], prior[48:58] = w_pose, w_beta
+    prior = FO.prior_vec(U, P.dtype, w_pose, w_beta)
     A, g, c = [], [], []
-    for b in range(B):
+    for b in range(P.shape[0]):
         m = np.nonzero(matched[b])[0]
         cv = torch.from_numpy(idx[b, m].astype(np.int64))
         w = torch.from_numpy(np.asarray(weights[b, m], dtype=np.float64))

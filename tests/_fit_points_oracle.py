@@ -11,9 +11,10 @@ import math
 import numpy as np
 import torch
 
+import _fit_oracle as FO
 import _fit_verts_oracle as VO
 
-U, NM = VO.U, VO.NM
+U = VO.U
 CHUNK = 512      # points per block of the distance table
 
 
@@ -107,19 +108,29 @@ def icp(model, points, weights, P0, rounds, iters, max_dist=np.inf, lambda0=1e-3
     """-> P [B,62] fp64, accepted [B], the data cost of every assignment [rounds + 1, B] (the last one at the returned P)
     and that last assignment; with history also the P of every assignment [rounds + 1, B, 62].  A round: assign at P's model points (fp64), then _fit_verts_oracle.lm on (vtarget, vw); a
     hand with a NaN vw row keeps its P."""
+    return icp_loop(model, points, weights, P0, rounds, max_dist, history,
+                    lambda vt, vw, n, P: VO.lm(model, vt, vw, P, iters, lambda0, w_pose, w_beta, free))
+
+
+def icp_loop(model, points, weights, P0, rounds, max_dist, history, solve, normals=None, assign_cost=None):
+    """the per-hand ICP of icp above and of _fit_plane_oracle.icp, which imports this module.  solve(vtarget, vw, n, P) ->
+    P, cost, accepted: the fit of a round.  normals(x) -> n, the model points' normals for the solve and the cost, and
+    assign_cost(x, a, n) -> [B], the data cost of an assignment in place of its stats[:, 3] (the plane fit's); an
+    unusable hand's is +inf in either."""
     P = P0.double().clone()
-    B = P.shape[0]
-    acc, costs, Ps = torch.zeros(B, dtype=torch.int32), [], []
+    acc, costs, Ps = torch.zeros(P.shape[0], dtype=torch.int32), [], []
     for r in range(rounds + 1):
         Ps.append(P.clone())
         with torch.no_grad():
-            a = assign(VO.model_verts(model, P).numpy(), points, weights, max_dist)
-        costs.append(a["stats"][:, 3].copy())
+            x = VO.model_verts(model, P).numpy()
+        a = assign(x, points, weights, max_dist)
+        n = None if normals is None else normals(x)
+        costs.append(np.where(a["stats"][:, 0] != 0, np.inf, a["stats"][:, 3] if assign_cost is None else assign_cost(x, a, n)))
         if r == rounds:
             break
         ok = torch.from_numpy(np.isfinite(a["vw"]).all(1))
         vw = torch.from_numpy(np.where(np.isfinite(a["vw"]), a["vw"], 0.0))
-        Pn, _, an = VO.lm(model, torch.from_numpy(a["vtarget"]), vw, P, iters, lambda0, w_pose, w_beta, free)
+        Pn, _, an = solve(torch.from_numpy(a["vtarget"]), vw, n, P)
         P = torch.where(ok.unsqueeze(1), Pn, P)
         acc += torch.where(ok, an, torch.zeros_like(an))
     return (P, acc, np.stack(costs), a) + ((torch.stack(Ps),) if history else ())
@@ -128,23 +139,14 @@ def icp(model, points, weights, P0, rounds, iters, max_dist=np.inf, lambda0=1e-3
 def point_normal_equations(model, P, points, weights, idx, matched, w_pose, w_beta):
     """the Gauss-Newton system of sum_n w_n |model_c(n) - q_n|^2 + priors with one row triple per matched point (rows
     J_c(n), residual model_c(n) - q_n) -> A [B,62,62], g [B,62], cost [B]: what the per-vertex form must reproduce"""
-    B, dt = P.shape[0], P.dtype
-    x, jm = VO.verts_jac(model, P)
-    V = x.shape[1]
-    s = torch.exp(P[:, 61]).reshape(B, 1, 1)
-    Jf = torch.zeros(B, 3 * V, U, dtype=dt)
-    Jf[:, :, :NM] = s * jm
-    Jf[:, :, 58:61] = torch.eye(3, dtype=dt).repeat(V, 1).unsqueeze(0)
-    Jf[:, :, 61] = (s * x).reshape(B, 3 * V)
-    mv = s * x + P[:, None, 58:61]
-    prior = torch.zeros(U, dtype=dt)
-    prior[3:48], prior[48:58] = w_pose, w_beta
+    Jf, mv = VO.rows(model, P, 0.0)
+    prior = FO.prior_vec(U, P.dtype, w_pose, w_beta)
     A, g, c = [], [], []
-    for b in range(B):
+    for b in range(P.shape[0]):
         n = np.nonzero(matched[b])[0]
         cv = torch.from_numpy(idx[b, n].astype(np.int64))
         w = torch.from_numpy(np.asarray(weights[b, n], dtype=np.float64)).repeat_interleave(3)
-        J = Jf[b].reshape(V, 3, U)[cv].reshape(-1, U)
+        J = Jf[b][cv].reshape(-1, U)
         r = (mv[b][cv] - torch.from_numpy(np.asarray(points[b, n], dtype=np.float64))).reshape(-1)
         A.append(J.T @ (w.unsqueeze(1) * J) + torch.diag(prior))
         g.append(J.T @ (w * r) + prior * P[b])

@@ -1,13 +1,11 @@
 """fp64 torch statement of the MANO fit to a track of meshes and to a track of point clouds
 (include/scat_mano_fit_seq_verts.h): the cost, the dense (62 T)^2 normal equations with the per-frame blocks of
-_fit_verts_oracle (Euclidean) or _fit_plane_oracle (the plane metric) and the smoothness exactly where
-_fit_seq_oracle.normal_equations places it, Levenberg-Marquardt with one lambda and one accept / reject per sequence and a
-dense Cholesky as _fit_seq_oracle.lm, the start (_fit_verts_oracle.procrustes_start per frame, then _fit_seq_oracle.start's
-scan), and the ICP loop over a track with its bridging rule.  Test-only: imports none of scat_amd's kernels.
+_fit_verts_oracle (Euclidean) or _fit_plane_oracle (the plane metric) and the smoothness where _lm_oracle.chain places it
+for every track oracle, _lm_oracle.lm with one lambda and one accept / reject per sequence and a dense Cholesky, the start
+(the Procrustes over the vertices per frame, then _fit_seq_oracle.track_start's scan), and the ICP loop over a track with
+its bridging rule.  Test-only: imports none of scat_amd's kernels.
 
 P is [S,T,62], targets [S,T,V,3], w [S,T,V], n (normals) [S,T,V,3] or None; smooth is the five weights."""
-import math
-
 import numpy as np
 import torch
 
@@ -16,6 +14,7 @@ import _fit_plane_oracle as LO
 import _fit_points_oracle as PO
 import _fit_seq_oracle as SO
 import _fit_verts_oracle as VO
+import _lm_oracle as L
 
 U = FO.U
 ALL = (1 << U) - 1
@@ -27,139 +26,54 @@ def _flat(P, targets, w, n):
     return (P.reshape(S * T, U), targets.reshape(S * T, V, 3), w.reshape(S * T, V), None if n is None else n.reshape(S * T, V, 3))
 
 
-def frame_costs(model, P, targets, w, n, tau, w_pose, w_beta):
-    """[S,T]: every frame's data term and priors"""
+def cost(model, P, targets, w, n, tau, w_pose, w_beta, smooth):
+    """[S]: the frames' costs (data term and priors), then the smoothness terms (a frozen unknown's count too)"""
     S, T = P.shape[:2]
     Pf, X, wf, nf = _flat(P, targets, w, n)
     c = VO.cost(model, Pf, X, wf, w_pose, w_beta) if n is None else LO.cost(model, Pf, X, wf, nf, tau, w_pose, w_beta)
-    return c.reshape(S, T)
+    return c.reshape(S, T).sum(1) + L.smooth_cost(P, SO.dvec(smooth, P.dtype))
 
 
-def cost(model, P, targets, w, n, tau, w_pose, w_beta, smooth):
-    """[S]: the frames' costs, then the smoothness terms (a frozen unknown's count too)"""
-    c = frame_costs(model, P, targets, w, n, tau, w_pose, w_beta).sum(1)
-    if P.shape[1] > 1:
-        e = P[:, 1:] - P[:, :-1]
-        c = c + (SO.dvec(smooth, P.dtype) * e * e).sum((1, 2))
-    return c
-
-
-def frame_equations(model, P, targets, w, n, tau, w_pose, w_beta, free=ALL):
-    """-> A [S,T,62,62] (undamped), g [S,T,62]: the frames' own normal equations"""
+def equations(model, P, targets, w, n, tau, w_pose, w_beta, smooth, free=ALL):
+    """-> H [S,62T,62T] (undamped, dense), g [S,62T]: _lm_oracle.chain of the frames' own A_t and g_t with D =
+    _fit_seq_oracle.dvec, which has a zero where the unknown is frozen"""
     S, T = P.shape[:2]
     Pf, X, wf, nf = _flat(P, targets, w, n)
     if n is None:
         A, g, _ = VO.normal_equations(model, Pf, X, wf, w_pose, w_beta, free)
     else:
         A, g, _ = LO.normal_equations(model, Pf, X, wf, nf, tau, w_pose, w_beta, free)
-    return A.reshape(S, T, U, U), g.reshape(S, T, U)
+    return L.chain(A.reshape(S, T, U, U), g.reshape(S, T, U), P, SO.dvec(smooth, P.dtype) * SO.free_vec(free, P.dtype))
 
 
 def normal_equations(model, P, targets, w, n, tau, w_pose, w_beta, smooth, free=ALL):
-    """-> H [S,62T,62T] (undamped, dense), g [S,62T], cost [S] at P: the frames' A_t and g_t on the diagonal, c_t D added to
-    A_t's diagonal and D ((p_t - p_t-1) + (p_t - p_t+1)) to g_t, -D beside the diagonal; D has a zero where the unknown is
-    frozen"""
-    S, T = P.shape[:2]
-    dt = P.dtype
-    A, g = frame_equations(model, P, targets, w, n, tau, w_pose, w_beta, free)
-    g = g.clone()
-    d = SO.dvec(smooth, dt) * SO.free_vec(free, dt)
-    H = torch.zeros(S, T * U, T * U, dtype=dt)
-    for t in range(T):
-        sl = slice(t * U, (t + 1) * U)
-        nb = (t > 0) + (t < T - 1)
-        H[:, sl, sl] = A[:, t] + torch.diag(nb * d)
-        if t > 0:
-            g[:, t] += d * (P[:, t] - P[:, t - 1]).detach()
-            H[:, sl, (t - 1) * U:t * U] = torch.diag(-d)
-            H[:, (t - 1) * U:t * U, sl] = torch.diag(-d)
-        if t < T - 1:
-            g[:, t] += d * (P[:, t] - P[:, t + 1]).detach()
+    """-> H, g of equations above and the cost [S] at P"""
     with torch.no_grad():
         c = cost(model, P, targets, w, n, tau, w_pose, w_beta, smooth)
-    return H, g.reshape(S, T * U), c
+    return equations(model, P, targets, w, n, tau, w_pose, w_beta, smooth, free) + (c,)
 
 
 def lm(model, targets, w, P0, iters, smooth, n=None, tau=1.0, lambda0=1e-3, w_pose=1e-6, w_beta=1e-6, free=ALL, history=False):
-    """-> P [S,T,62], cost [S], accepted [S] (and the per-iteration costs [iters,S]) in P0's dtype: _fit_seq_oracle.lm's
-    loop on the equations above"""
+    """-> P [S,T,62], cost [S], accepted [S] (and the per-iteration costs [iters,S]) in P0's dtype: _lm_oracle.lm"""
     dt = P0.dtype
     targets, w = targets.to(dt), w.to(dt)
     n = None if n is None else n.to(dt)
-    P = P0.clone()
-    S, T = P.shape[:2]
-    N = T * U
-    lam = torch.full((S,), lambda0, dtype=dt)
-    acc = torch.zeros(S, dtype=torch.int32)
-    fr = SO.free_vec(free, dt).repeat(T)
-    hist, c = [], None
-    for _ in range(iters):
-        H, g, c = normal_equations(model, P, targets, w, n, tau, w_pose, w_beta, smooth, free)
-        Hd = H + lam.reshape(S, 1, 1) * torch.diag_embed(torch.diagonal(H, dim1=1, dim2=2))
-        L, info = torch.linalg.cholesky_ex(Hd)
-        ok = info == 0
-        L = torch.where(ok.reshape(S, 1, 1), L, torch.eye(N, dtype=dt).expand(S, N, N))
-        delta = -torch.cholesky_solve(g.unsqueeze(2), L).squeeze(2) * fr
-        Pt = P + delta.reshape(S, T, U)
-        with torch.no_grad():
-            ct = cost(model, Pt, targets, w, n, tau, w_pose, w_beta, smooth)
-        take = ok & torch.isfinite(Pt).reshape(S, -1).all(1) & (ct < c)
-        P = torch.where(take.reshape(S, 1, 1), Pt, P)
-        c = torch.where(take, ct, c)
-        acc += take.to(torch.int32)
-        lam = torch.where(take, (lam * 0.1).clamp_min(FO.LAMBDA_MIN), (lam * 10).clamp_max(FO.LAMBDA_MAX))
-        hist.append(c.clone())
-    return (P, c, acc, torch.stack(hist)) if history else (P, c, acc)
+    return L.lm(P0, iters, lambda0, lambda P: equations(model, P, targets, w, n, tau, w_pose, w_beta, smooth, free),
+                lambda P: cost(model, P, targets, w, n, tau, w_pose, w_beta, smooth), SO.free_vec(free, dt))[:4 if history else 3]
 
 
 def procrustes(model, targets, w, dt=torch.float64):
     """_fit_verts_oracle.procrustes_start's formulas [B,62] fp64, on zero-pose vertices computed in dt (the kernel's are
     fp32; the Procrustes itself is fp64 whatever dt, as in the kernel); tests/test_fit_seq_verts.py holds the fp64 form to
     _fit_verts_oracle.procrustes_start"""
-    Y, w = targets.double(), w.double()
-    B = Y.shape[0]
-    with torch.no_grad():
-        X = VO.verts(model, torch.zeros(1, U, dtype=dt)).double().expand(B, -1, 3)
-    W = w.sum(1).reshape(B, 1)
-    mx, my = (w.unsqueeze(2) * X).sum(1) / W, (w.unsqueeze(2) * Y).sum(1) / W
-    Xc, Yc = X - mx.unsqueeze(1), Y - my.unsqueeze(1)
-    K = torch.einsum("bj,bja,bjc->bac", w, Xc, Yc)
-    Uu, _, Vh = torch.linalg.svd(K)
-    d = torch.sign(torch.linalg.det(Vh.transpose(1, 2) @ Uu.transpose(1, 2)))
-    R = Vh.transpose(1, 2) @ torch.diag_embed(torch.stack([torch.ones_like(d), torch.ones_like(d), d], 1)) @ Uu.transpose(1, 2)
-    sc = torch.einsum("bca,bac->b", R, K) / (w * (Xc * Xc).sum(2)).sum(1)
-    P = torch.zeros(B, U, dtype=torch.float64)
-    P[:, 0:3] = FO.rot_to_axis_angle(R)
-    P[:, 58:61] = my - sc.reshape(B, 1) * (R @ mx.unsqueeze(2)).squeeze(2)
-    P[:, 61] = torch.log(sc)
-    return P
+    X = VO.verts(model, torch.zeros(1, U, dtype=dt)).double().expand(targets.shape[0], -1, 3)
+    return FO.similarity_start(X, targets.double(), w.double())
 
 
 def start(model, targets, w, dt=torch.float64):
-    """init = 1: the Procrustes start over the vertices frame by frame; a frame of total weight zero takes the start of the
-    frame before it, frame 0 that of the first frame with weight, zeros if there is none; then for t >= 1 rots_t becomes
-    r (1 - 2 pi / |r|) when that is closer to rots_t-1: _fit_seq_oracle.start's scan.  -> [S,T,62] in dt"""
-    S, T, V = targets.shape[:3]
-    w = w.double()
-    has = w.sum(2) > 0
-    wf = torch.where(has.unsqueeze(2), w, torch.ones_like(w)).reshape(S * T, V)
-    P = procrustes(model, targets.reshape(S * T, V, 3), wf, dt).reshape(S, T, U)
-    for s in range(S):
-        idx = [t for t in range(T) if bool(has[s, t])]
-        if not idx:
-            P[s] = 0.0
-            continue
-        for t in range(T):
-            if not bool(has[s, t]):
-                P[s, t] = P[s, t - 1] if t > 0 else P[s, idx[0]]
-            elif t > 0:
-                r = P[s, t, :3]
-                nr = float(r.norm())
-                if nr > 0.0:
-                    alt = r * (1.0 - 2.0 * math.pi / nr)
-                    if float(((alt - P[s, t - 1, :3]) ** 2).sum()) < float(((r - P[s, t - 1, :3]) ** 2).sum()):
-                        P[s, t, :3] = alt
-    return P.to(dt)
+    """init = 1 -> [S,T,62] in dt: _fit_seq_oracle.track_start (the Procrustes start frame by frame, then the scan for the
+    frames without weight and the rotations' unwrapping) on the zero-pose vertices computed in dt"""
+    return SO.track_start(VO.verts(model, torch.zeros(1, U, dtype=dt)), targets, w).to(dt)
 
 
 def meshes(model, P):

@@ -1,47 +1,26 @@
 """fp64 torch statement of the MANO fit to a full mesh of include/scat_mano_fit_verts.h on top of _mano_oracle.forward:
 the model vertices, the cost, the Jacobian (torch.autograd.functional.jacobian, forward mode: 58 columns are fewer than
-3 V rows), the Procrustes start over the vertices and the Levenberg-Marquardt loop with the schedule of
-_fit_oracle.lm (Marquardt scaling, accept only if the cost drops, lambda / 10 or x 10 within 1e-12..1e12, a failed
-Cholesky is a rejection, frozen unknowns are unit rows).  Test-only: imports none of scat_amd's kernels.
+3 V rows), the vertex rows and the normal equations; the Procrustes start over the vertices and the Levenberg-Marquardt
+loop are _lm_oracle's, as for _fit_oracle.  Test-only: imports none of scat_amd's kernels.
 
 Everything takes a dtype.  In fp64 the vertices are _mano_oracle.forward's; in fp32 they come from verts_any below, the
 same formulas in the tensors' own dtype, which exists only to measure what fp32 rounding does to a result: the GPU gates
 are 4 x the error of this fp32 run against the fp64 run on the same inputs (tests/test_fit_verts.py holds verts_any to
 _mano_oracle.forward in fp64)."""
-import numpy as np
 import torch
 
 import _fit_oracle as FO
+import _lm_oracle as L
 import _mano_oracle as MO
 
 U, NM = FO.U, FO.NM
 LAMBDA_MIN, LAMBDA_MAX = FO.LAMBDA_MIN, FO.LAMBDA_MAX
+rel = MO.rel
 
 
 def verts_any(model, rots, poses, betas):
-    """rows 21.. of _mano_oracle.forward in the inputs' dtype; the model's fp32 arrays are exact in either"""
-    dt = rots.dtype
-    T = lambda a: torch.from_numpy(np.asarray(a)).to(dt)
-    vt, sd, pd = T(model.v_template), T(model.shapedirs), T(model.posedirs)
-    Jr, W, hm = T(model.J_regressor), T(model.weights), T(model.hands_mean)
-    parents = list(model.parents)
-    B = rots.shape[0]
-    pose = torch.cat([torch.zeros(B, 1, 3, dtype=dt), (hm.reshape(1, 45) + poses).reshape(B, 15, 3)], dim=1)
-    R = FO.rodrigues_any(pose.reshape(-1, 3)).reshape(B, 16, 3, 3)
-    v_shaped = vt.unsqueeze(0) + torch.einsum("vck,bk->bvc", sd, betas)
-    J = torch.einsum("jv,bvc->bjc", Jr, v_shaped)
-    pw = (R[:, 1:] - torch.eye(3, dtype=dt)).reshape(B, 135)
-    vp = v_shaped + torch.einsum("vck,bk->bvc", pd, pw)
-    RG, t = [R[:, 0]], [J[:, 0]]
-    for i in range(1, 16):
-        p = parents[i]
-        RG.append(RG[p] @ R[:, i])
-        t.append((RG[p] @ (J[:, i] - J[:, p]).unsqueeze(2)).squeeze(2) + t[p])
-    RG, t = torch.stack(RG, 1), torch.stack(t, 1)
-    a = t - (RG @ J.unsqueeze(3)).squeeze(3)
-    TR = torch.einsum("vi,birc->bvrc", W, RG)
-    Ta = torch.einsum("vi,bir->bvr", W, a)
-    v = (TR @ vp.unsqueeze(3)).squeeze(3) + Ta
+    """rows 21.. of _mano_oracle.forward in the inputs' dtype: the rotated joint 1 subtracted from the rotated vertices"""
+    t, v = FO.skinned_any(model, rots, poses, betas, slice(None))
     Rg = FO.rodrigues_any(rots).transpose(1, 2)
     return v @ Rg - t[:, 1:2] @ Rg
 
@@ -84,81 +63,24 @@ def rms(model, P, targets):
 
 
 def procrustes_start(model, targets, w):
-    """init = 1: zeros for pose and shape, the weighted similarity Procrustes (SVD form) of the zero-pose vertices onto the
-    targets for rots, trans, log_scale.  fp64 whatever the targets' dtype, as in the kernel."""
-    T, w = targets.double(), w.double()
-    B = T.shape[0]
-    P = torch.zeros(B, U, dtype=torch.float64)
-    X = verts(model, P)
-    W = w.sum(1).reshape(B, 1)
-    mx, my = (w.unsqueeze(2) * X).sum(1) / W, (w.unsqueeze(2) * T).sum(1) / W
-    Xc, Tc = X - mx.unsqueeze(1), T - my.unsqueeze(1)
-    K = torch.einsum("bj,bja,bjc->bac", w, Xc, Tc)           # sum_v w x y^T
-    Uu, S, Vh = torch.linalg.svd(K)
-    d = torch.sign(torch.linalg.det(Vh.transpose(1, 2) @ Uu.transpose(1, 2)))
-    D = torch.diag_embed(torch.stack([torch.ones_like(d), torch.ones_like(d), d], 1))
-    R = Vh.transpose(1, 2) @ D @ Uu.transpose(1, 2)          # y ~ R x
-    var = (w * (Xc * Xc).sum(2)).sum(1)
-    sc = torch.einsum("bca,bac->b", R, K) / var
-    P[:, 0:3] = FO.rot_to_axis_angle(R)
-    P[:, 58:61] = my - sc.reshape(B, 1) * (R @ mx.unsqueeze(2)).squeeze(2)
-    P[:, 61] = torch.log(sc)
-    return P
+    """init = 1: _fit_oracle.similarity_start of the zero-pose vertices, computed in fp64; fp64 whatever the targets' dtype"""
+    X = verts(model, torch.zeros(targets.shape[0], U, dtype=torch.float64))
+    return FO.similarity_start(X, targets.double(), w.double())
+
+
+def rows(model, P, targets):
+    """_fit_oracle.rows of every vertex: Jf [B,V,3,62] and r [B,V,3]"""
+    return FO.rows(*verts_jac(model, P), P, targets)
 
 
 def normal_equations(model, P, targets, w, w_pose, w_beta, free):
-    """-> A [B,62,62] (undamped), g [B,62], cost [B] at P, the frozen unknowns as unit rows with g = 0"""
-    B, dt = P.shape[0], P.dtype
-    x, jm = verts_jac(model, P)
-    V = x.shape[1]
-    s = torch.exp(P[:, 61]).reshape(B, 1, 1)
-    Jf = torch.zeros(B, 3 * V, U, dtype=dt)
-    Jf[:, :, :NM] = s * jm
-    Jf[:, :, 58:61] = torch.eye(3, dtype=dt).repeat(V, 1).unsqueeze(0)
-    Jf[:, :, 61] = (s * x).reshape(B, 3 * V)
-    r = (s * x + P[:, None, 58:61] - targets).reshape(B, 3 * V)
-    wr = w.repeat_interleave(3, dim=1)
-    prior = torch.zeros(U, dtype=dt)
-    prior[3:48], prior[48:58] = w_pose, w_beta
-    A = Jf.transpose(1, 2) @ (wr.unsqueeze(2) * Jf) + torch.diag(prior)
-    g = (Jf.transpose(1, 2) @ (wr * r).unsqueeze(2)).squeeze(2) + prior * P
-    c = (wr * r * r).sum(1) + w_pose * (P[:, 3:48] ** 2).sum(1) + w_beta * (P[:, 48:58] ** 2).sum(1)
-    fr = torch.tensor([(free >> i) & 1 for i in range(U)], dtype=torch.bool)
-    keep = (fr[:, None] & fr[None, :]).to(dt)
-    A = A * keep + torch.diag((~fr).to(dt))
-    return A, g * fr.to(dt), c
+    """-> A [B,62,62] (undamped), g [B,62], cost [B] at P: _fit_oracle.row_equations of the vertices"""
+    return FO.row_equations(*rows(model, P, targets), w, P, w_pose, w_beta, free)
 
 
 def lm(model, targets, w, P0, iters, lambda0=1e-3, w_pose=1e-6, w_beta=1e-6, free=(1 << U) - 1, history=False):
-    """-> P [B,62], cost [B], accepted [B] (and the per-iteration costs [iters,B]) in P0's dtype; _fit_oracle.lm's schedule"""
+    """-> P [B,62], cost [B], accepted [B] (and the per-iteration costs [iters,B]) in P0's dtype: _lm_oracle.lm"""
     dt = P0.dtype
     targets, w = targets.to(dt), w.to(dt)
-    P = P0.clone()
-    B = P.shape[0]
-    lam = torch.full((B,), lambda0, dtype=dt)
-    acc = torch.zeros(B, dtype=torch.int32)
-    fr = torch.tensor([(free >> i) & 1 for i in range(U)], dtype=dt)
-    hist, c = [], None
-    for _ in range(iters):
-        A, g, _ = normal_equations(model, P, targets, w, w_pose, w_beta, free)
-        with torch.no_grad():      # by the same expression as the trial's, so that a rejected step leaves the same bits
-            c = cost(model, P, targets, w, w_pose, w_beta)
-        Ad = A + lam.reshape(B, 1, 1) * torch.diag_embed(torch.diagonal(A, dim1=1, dim2=2))
-        L, info = torch.linalg.cholesky_ex(Ad)
-        ok = info == 0
-        L = torch.where(ok.reshape(B, 1, 1), L, torch.eye(U, dtype=dt).expand(B, U, U))
-        delta = -torch.cholesky_solve(g.unsqueeze(2), L).squeeze(2) * fr
-        Pt = P + delta
-        with torch.no_grad():
-            ct = cost(model, Pt, targets, w, w_pose, w_beta)
-        take = ok & torch.isfinite(Pt).all(1) & (ct < c)
-        P = torch.where(take.unsqueeze(1), Pt, P)
-        c = torch.where(take, ct, c)
-        acc += take.to(torch.int32)
-        lam = torch.where(take, (lam * 0.1).clamp_min(LAMBDA_MIN), (lam * 10).clamp_max(LAMBDA_MAX))
-        hist.append(c.clone())
-    return (P, c, acc, torch.stack(hist)) if history else (P, c, acc)
-
-
-def rel(a, b):
-    return MO.rel(a, b)
+    return L.lm(P0, iters, lambda0, lambda P: normal_equations(model, P, targets, w, w_pose, w_beta, free)[:2],
+                lambda P: cost(model, P, targets, w, w_pose, w_beta), L.mask_vec(free, U, dt))[:4 if history else 3]
