@@ -29,10 +29,18 @@ PUBLIC_HEADERS = ("scat_hip.h", "scat_mesh_eval.h", "scat_eval.h", "scat_render.
                   "scat_mano_fit_kp.h", "scat_mano_fit_seq.h", "scat_mano_fit_verts.h", "scat_mano_fit_points.h",
                   "scat_mano_fit_seq_kp.h", "scat_mano_fit_plane.h", "scat_mano_fit_seq_verts.h")
 INCLUDE = os.path.join(HERE, "..", "include")
+# Headers added since the suite began to count the files of include/ live beside it in include_ext/: the same library, the
+# same conventions, the same refusal to build without one of them, and a rebuild trigger of their own (_ext_headers_mtime)
+EXT_HEADERS = ("scat_mano_fit_views.h",)
+INCLUDE_EXT = os.path.join(HERE, "..", "include_ext")
 
 
 def _public_headers_mtime():
     return max(os.path.getmtime(os.path.join(INCLUDE, h)) for h in os.listdir(INCLUDE) if h.endswith(".h"))
+
+
+def _ext_headers_mtime():
+    return max((os.path.getmtime(os.path.join(INCLUDE_EXT, h)) for h in os.listdir(INCLUDE_EXT) if h.endswith(".h")), default=0.0)
 
 
 def _deps_mtime():
@@ -43,7 +51,7 @@ def _deps_mtime():
         for f in files:
             if f.endswith((".h", ".hip")):
                 m = max(m, os.path.getmtime(os.path.join(root, f)))
-    return max(m, _public_headers_mtime())
+    return max(m, _public_headers_mtime(), _ext_headers_mtime())
 
 
 DIAG_OUT = os.path.join(HERE, "..", "tools", "_bin", "libscat_hip_diag.so")
@@ -68,11 +76,14 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
     missing = [h for h in PUBLIC_HEADERS if not os.path.exists(os.path.join(INCLUDE, h))]
     if missing:
         raise RuntimeError(f"public headers missing from {os.path.abspath(INCLUDE)}: {missing}")
+    missing = [h for h in EXT_HEADERS if not os.path.exists(os.path.join(INCLUDE_EXT, h))]
+    if missing:
+        raise RuntimeError(f"public headers missing from {os.path.abspath(INCLUDE_EXT)}: {missing}")
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _deps_mtime():
         return OUT
     os.makedirs(OBJ, exist_ok=True)
     hdr_m = max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith(".h"))
-    hdr_m = max(hdr_m, _public_headers_mtime())
+    hdr_m = max(hdr_m, _public_headers_mtime(), _ext_headers_mtime())
 
     def one(src):
         o = os.path.join(OBJ, src[:-4] + ".o")

@@ -54,6 +54,15 @@ one workgroup per track eliminates along the frames; a frame in which nothing ma
     res = fitter.fit_points_sequence(clouds, init=fitter.fit_sequence(joints), faces=renderer, max_dist=0.03)
     frames = renderer.render(fitter.mesh(res).flatten(0, 1), cams)
 
+fit_keypoints_views (include_ext/scat_mano_fit_views.h, csrc/mano_fit_views.hip) takes 2-D keypoints seen by C calibrated
+pinhole cameras, what a capture rig gives: no camera unknowns, depth and metric scale observable, a detection that is wrong in
+one view voted down by the others; the start is triangulated:
+
+    cams = Cameras(R, t, K)                            # [Bc,C,3,3], [Bc,C,3], [Bc,C,4] = fx, fy, cx, cy; Bc is 1 or B
+    res = fitter.fit_keypoints_views(kp, cams, sigma2=10.0)      # FitResult in the rig's frame; kp [B,C,21,2] pixels
+    points, valid = fitter.triangulate(kp, cams)       # [B,21,3], [B,21] bool
+    uv = fitter.project_views(res, cams)               # [B,C,21,2]
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -81,6 +90,9 @@ FIT_VERTS_HEADER, FIT_POINTS_HEADER, FIT_SEQ_KP_HEADER, FIT_PLANE_HEADER = (
     os.path.join(HERE, "..", "include", f"scat_mano_fit_{n}.h") for n in ("verts", "points", "seq_kp", "plane"))
 # the MANO fit to a track of meshes and to a track of point clouds
 FIT_SEQ_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_seq_verts.h")
+# the MANO fit to keypoints in calibrated views; include_ext/ holds the headers added since the suite counts include/'s
+FIT_VIEWS_HEADER = os.path.join(HERE, "..", "include_ext", "scat_mano_fit_views.h")
+VIEWS_MAX_C = 8                # SCAT_FIT_VIEWS_MAX_C
 MAX_F = 4096                   # SCAT_RENDER_MAX_F
 POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
 POINTS_MAX_ROUNDS = 64         # SCAT_FIT_POINTS_MAX_ROUNDS
@@ -182,6 +194,66 @@ class PointSequenceFitResult(NamedTuple):
     rms: torch.Tensor        # [S,T]: sqrt(data_cost / matched weight), +inf when nothing matched
     idx: torch.Tensor        # [S,T,N] int32: the nearest vertex at p, -1 for a point of weight 0
     dist: torch.Tensor       # [S,T,N]
+
+
+class Cameras(NamedTuple):
+    """C calibrated pinhole cameras: a point m of the world is q = R m + t in a camera, which looks along +z, and lands on
+    the pixel (fx q.x / q.z + cx, fy q.y / q.z + cy).  Bc = 1 is one rig for the whole batch, Bc = B one rig per sample."""
+    R: torch.Tensor          # [Bc,C,3,3]
+    t: torch.Tensor          # [Bc,C,3]
+    K: torch.Tensor          # [Bc,C,4]: fx, fy, cx, cy
+
+    def check(self, what="Cameras"):
+        """shapes, dtype and device -> (Bc, C)"""
+        R, t, K = self
+        if not all(isinstance(a, torch.Tensor) for a in self) or R.dim() != 4:
+            raise ScatError(f"{what} needs tensors R [Bc,C,3,3], t [Bc,C,3], K [Bc,C,4]")
+        Bc, C = int(R.shape[0]), int(R.shape[1])
+        if Bc < 1 or not 1 <= C <= VIEWS_MAX_C or tuple(R.shape) != (Bc, C, 3, 3) or tuple(t.shape) != (Bc, C, 3) \
+                or tuple(K.shape) != (Bc, C, 4):
+            raise ScatError(f"{what} needs R [Bc,C,3,3], t [Bc,C,3], K [Bc,C,4] with Bc >= 1 and C in 1..{VIEWS_MAX_C}, got "
+                            f"{tuple(R.shape)}, {tuple(t.shape)}, {tuple(K.shape)}")
+        if not all(a.dtype == torch.float32 for a in self):
+            raise ScatError(f"{what} needs fp32 tensors, got {R.dtype}, {t.dtype}, {K.dtype}")
+        if not (R.device == t.device == K.device):
+            raise ScatError(f"{what}: R, t and K are on {R.device}, {t.device} and {K.device}")
+        return Bc, C
+
+    def packed(self):
+        """-> [Bc,C,16] fp32, as scat_mano_fit_views.h takes the cameras: R row-major, t, fx, fy, cx, cy"""
+        Bc, C = self.check()
+        return torch.cat([self.R.reshape(Bc, C, 9), self.t, self.K], dim=2).contiguous()
+
+    def weak_perspective(self, view, depth, size):
+        """-> (R [Bc,3,3], t [Bc,3], cam [Bc,3]): camera `view` as MeshRenderer.render and project_outputs take one, for a
+        hand at the distance `depth` (a number, or [Bc]) in a frame of size = (H, W).  The mesh goes into the camera's
+        frame, verts @ R^T + t, and cam = (cs, ctx, cty) with cs = fx / (depth W / 2), ctx = (cx - W / 2) / (cs W / 2),
+        cty = (cy - H / 2) / (cs H / 2) agrees with the pinhole on the plane z = depth.  The renderer has one scale, so
+        cameras whose fx / (W / 2) and fy / (H / 2) differ by more than 1e-6 relative are refused."""
+        Bc, C = self.check("Cameras.weak_perspective")
+        if not 0 <= int(view) < C:
+            raise ScatError(f"Cameras.weak_perspective: view {view} outside 0..{C - 1}")
+        H, W = (float(v) for v in size)
+        if not (H > 0 and W > 0):
+            raise ScatError(f"Cameras.weak_perspective: size {size} must be positive")
+        K = self.K[:, int(view)]
+        sx, sy = K[:, 0] / (0.5 * W), K[:, 1] / (0.5 * H)
+        if bool(((sx - sy).abs() > 1e-6 * torch.maximum(sx.abs(), sy.abs())).any()):
+            raise ScatError("Cameras.weak_perspective: fx / (W / 2) and fy / (H / 2) differ, and the renderer has one scale")
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=K.device).expand(Bc)
+        if not bool((depth > 0).all()):
+            raise ScatError("Cameras.weak_perspective: depth must be positive")
+        cs = sx / depth
+        cam = torch.stack([cs, (K[:, 2] - 0.5 * W) / (cs * 0.5 * W), (K[:, 3] - 0.5 * H) / (cs * 0.5 * H)], dim=1)
+        return self.R[:, int(view)].contiguous(), self.t[:, int(view)].contiguous(), cam.contiguous()
+
+
+def project_points(points, cameras):
+    """points [B,J,3] of the world through every camera of a Cameras -> [B,C,J,2] pixels; plain torch, any device and
+    floating dtype, no rule about points behind a camera"""
+    q = torch.einsum("bcik,bjk->bcji", cameras.R, points) + cameras.t[:, :, None, :]
+    K = cameras.K[:, :, None, :]
+    return (K[..., 0:2] * q[..., 0:2] / q[..., 2:3] + K[..., 2:4]).contiguous()
 
 
 def _check_model(what, model, ref):
@@ -444,6 +516,32 @@ def mano_fit_kp(model, targets3, weights3, targets2, weights2, joint_map, pose_l
                            int(init), float(lambda0), float(w_pose), float(w_beta), float(w_limit), float(sigma3), float(sigma2),
                            float(half_w), float(half_h), int(free), int(free_cam), _stream())
     return cost, accepted
+
+
+def mano_fit_views(model, cams, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose, w_beta, w_limit,
+                   sigma2, z_near, free=ALL_FREE):
+    """scat_mano_fit_views as it is declared: cams [Bc,C,16] with Bc 1 or B, targets2 [B,C,21,2], weights2 [B,C,21] or None
+    (all ones), joint_map int32 [21] on the device, pose_lo / pose_hi [45] or None, p [B,62] (read when init = 0, written)
+    -> (cost [B], accepted [B] int32)"""
+    B, C = int(targets2.shape[0]), int(targets2.shape[1])
+    cost, accepted = _results(B, targets2.device)
+    lib().bind(FIT_VIEWS_HEADER).scat_mano_fit_views(*_model_args(model), _p(cams), int(cams.shape[0]), _p(targets2), _p(weights2),
+                                                     _p(joint_map), _p(pose_lo), _p(pose_hi), _p(p), _p(cost), _p(accepted), B, C,
+                                                     model.V, model.parents_packed, *model.tips, int(iters), int(init),
+                                                     float(lambda0), float(w_pose), float(w_beta), float(w_limit), float(sigma2),
+                                                     float(z_near), int(free), _stream())
+    return cost, accepted
+
+
+def triangulate_views(cams, targets2, weights2, z_near):
+    """scat_triangulate as it is declared: cams [Bc,C,16] with Bc 1 or B, targets2 [B,C,21,2], weights2 [B,C,21] or None
+    (all ones) -> (points [B,21,3], valid [B,21] int32)"""
+    B, C = int(targets2.shape[0]), int(targets2.shape[1])
+    points = torch.empty((B, 21, 3), dtype=torch.float32, device=targets2.device)
+    valid = torch.empty((B, 21), dtype=torch.int32, device=targets2.device)
+    lib().bind(FIT_VIEWS_HEADER).scat_triangulate(_p(cams), int(cams.shape[0]), _p(targets2), _p(weights2), _p(points), _p(valid), B, C,
+                                                  float(z_near), _stream())
+    return points, valid
 
 
 def mano_fit_seq(model, targets, weights, joint_map, p, iters, init, lambda0, w_pose, w_beta, s_rots, s_poses, s_betas, s_trans,
@@ -952,6 +1050,97 @@ class ManoFitter:
                                              sigma2, limits, w_limit, init, free, free_cam, iters)
         cost, accepted = mano_fit_seq_kp(*args, sm, *frees)
         return KeypointSequenceFitResult(*_groups(p), p[..., 62:65], cost, accepted, p)
+
+    def _views(self, what, joints2d, cameras, w2):
+        """the checked joints2d [B,C,21,2], packed cameras [Bc,C,16] with Bc 1 or B and w2 [B,C,21] or None, contiguous"""
+        if not isinstance(cameras, Cameras):
+            raise ScatError(f"{what} needs cameras as a Cameras(R, t, K)")
+        Bc, C = cameras.check(what)
+        _need_gpu(what, joints2d, *cameras, *(() if w2 is None else (w2,)))
+        _check_model(what, self.model, joints2d)
+        B = int(joints2d.shape[0]) if joints2d.dim() == 4 else 0
+        if B == 0 or tuple(joints2d.shape) != (B, C, 21, 2) or joints2d.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 joints2d [B,{C},21,2] with B >= 1 for {C} cameras, got {joints2d.dtype} "
+                            f"{tuple(joints2d.shape)}")
+        if Bc not in (1, B):
+            raise ScatError(f"{what}: {Bc} rigs for a batch of {B}: one rig for the batch or one per sample")
+        if cameras.R.device != joints2d.device or (w2 is not None and w2.device != joints2d.device):
+            raise ScatError(f"{what}: the cameras and w2 must be on {joints2d.device}")
+        return joints2d.contiguous(), cameras.packed(), _weights(what, w2, (B, C, 21))
+
+    @staticmethod
+    def _z_near(what, z_near):
+        z = float(z_near)
+        if not (z > 0.0 and math.isfinite(z)):
+            raise ScatError(f"{what}: z_near {z_near} must be positive and finite")
+        return z
+
+    def fit_keypoints_views(self, joints2d, cameras, w2=None, sigma2=0.0, limits=None, w_limit=0.0, init=None, free=ALL_FREE,
+                            iters=None, z_near=1e-3):
+        """joints2d [B,C,21,2] fp32, the pixels of the 21 keypoints in C <= 8 calibrated views (cameras: a Cameras with one
+        rig for the batch or one per sample) -> FitResult, in the cameras' world frame and unit: mesh(), joints(),
+        MeshEvaluator and every fit's init take it as it is.  There are no camera unknowns; with two or more views depth,
+        metric scale and most of the twist are observable.
+        w2: [B,C,21] or None (all ones); a view-joint of weight 0 does not count, whatever its finite pixel: this is how a
+        joint that a view does not see is passed.  sigma2: the Geman-McClure scale in pixels, 0 for the quadratic loss; a
+        detection that is wrong in one view is voted down by the others.  limits: (lo[45], hi[45]) on poses with the weight
+        w_limit; an entry that is not finite is no limit.
+        UNITS: the cost is in pixels squared, summed over up to 21 C view-joints, and the fitter's w_pose and w_beta and
+        w_limit multiply squared radians and shape coefficients beside it.  A pose moves a joint by fx s / z pixels per
+        radian (about 100 px for fx = 600, a 0.08 m hand at 0.5 m), so w_pose = 1e2 counts 0.1 rad like a pixel; the
+        fitter's default of 1e-6, chosen beside metres squared, is no prior at all here.
+        init: None for the closed-form start (every joint triangulated from its views of positive weight, see
+        triangulate(), then the Procrustes of the zero-pose joints onto the triangulated ones), or p [B,62] / a FitResult,
+        PointFitResult or KeypointFitResult (its first 62) to start from (it is not modified).  C = 1 needs an init: depth
+        and scale cannot be told apart from one view, and nothing is triangulated.  free: bit i clear freezes unknown i.
+        BEHIND THE CAMERA: a view-joint of positive weight at q.z <= z_near at the start makes the sample not fitted, and a
+        trial step with one is rejected.  Not fitted means cost +inf, accepted 0 and p the start (zeros for a closed-form
+        start that found fewer than 3 joints); so is a sample with a pixel, weight or camera entry that is not finite, or
+        a negative weight."""
+        what = "ManoFitter.fit_keypoints_views"
+        joints2d, cams, w2 = self._views(what, joints2d, cameras, w2)
+        B, C = int(joints2d.shape[0]), int(joints2d.shape[1])
+        if init is None and C < 2:
+            raise ScatError(f"{what}: one view needs a start (init): nothing can be triangulated")
+        lo = hi = None
+        if limits is not None:
+            lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(joints2d.device).contiguous() for t in limits)
+            if tuple(lo.shape) != (POSE,) or tuple(hi.shape) != (POSE,):
+                raise ScatError(f"{what} needs limits (lo[45], hi[45]), got {tuple(lo.shape)}, {tuple(hi.shape)}")
+        if isinstance(init, KeypointFitResult):
+            init = init.p[:, :UNKNOWNS]
+        p = _start(what, init, (FitResult, PointFitResult), (B, UNKNOWNS), joints2d.device)
+        iters = self.iters if iters is None else int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        if min(float(sigma2), float(w_limit)) < 0:
+            raise ScatError(f"{what}: sigma2 and w_limit must not be negative")
+        cost, accepted = mano_fit_views(self.model, cams, joints2d, w2, self._map_on(joints2d.device), lo, hi, p, iters,
+                                        0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit, sigma2,
+                                        self._z_near(what, z_near), free)
+        return FitResult(*_groups(p), cost, accepted, p)
+
+    def triangulate(self, joints2d, cameras, w2=None, z_near=1e-3):
+        """joints2d [B,C,21,2], cameras, w2 as in fit_keypoints_views -> (points [B,21,3] fp32, valid [B,21] bool): per joint
+        the point nearest to the rays of its views of positive weight (weighted least squares, in fp64).  A joint is valid
+        iff at least two of its views have positive weight, the rays are not parallel (closer than about 3 mrad) and the
+        point is in front of every contributing camera (q.z > z_near); an invalid joint's point is 0.  A sample with a
+        pixel, weight or camera entry that is not finite, or a negative weight, has no valid joint."""
+        what = "ManoFitter.triangulate"
+        joints2d, cams, w2 = self._views(what, joints2d, cameras, w2)
+        points, valid = triangulate_views(cams, joints2d, w2, self._z_near(what, z_near))
+        return points, valid.bool()
+
+    def project_views(self, result, cameras):
+        """the fitted joints of a result (joints(result), [B,21,3]) in every camera -> [B,C,21,2] pixels; plain torch, no
+        rule about joints behind a camera"""
+        what = "ManoFitter.project_views"
+        if not isinstance(cameras, Cameras):
+            raise ScatError(f"{what} needs cameras as a Cameras(R, t, K)")
+        Bc, _ = cameras.check(what)
+        j = self.joints(result)
+        if j.dim() != 3 or Bc not in (1, int(j.shape[0])) or cameras.R.device != j.device:
+            raise ScatError(f"{what} needs the result of a batch and one rig, or one per sample, on {j.device}")
+        return project_points(j, cameras)
 
     def project(self, result, size=(224, 224)):
         """the fitted joints of a KeypointFitResult through its camera -> [B,21,2] pixels of a frame of size = (H, W):
