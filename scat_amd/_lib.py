@@ -5,8 +5,9 @@ headers are the single source of truth for the C ABI. EXTENSION_HEADERS (scat_ma
 frames) are bound the same way beside them, and _Lib.bind(path) binds any further header of the library on first use
 (scat_mano_fit_verts.h, the MANO fit to a full mesh, scat_mano_fit_points.h, the MANO fit to a point cloud,
 scat_mano_fit_plane.h, the point-to-plane form of the latter, scat_mano_fit_seq_kp.h, the MANO fit to a track of
-keypoints, scat_mano_fit_seq_verts.h, the MANO fit to a track of meshes and of point clouds, and
-include_ext/scat_mano_fit_views.h, the MANO fit to keypoints in calibrated views, from scat_amd/fit.py).
+keypoints, scat_mano_fit_seq_verts.h, the MANO fit to a track of meshes and of point clouds,
+include_ext/scat_mano_fit_views.h, the MANO fit to keypoints in calibrated views, and
+include_ext/scat_mano_fit_seq_views.h, the MANO fit to a track of such keypoints, from scat_amd/fit.py).
 The product path has NO fallback: if the library is missing, importing a kernel raises."""
 from __future__ import annotations
 

@@ -32,6 +32,8 @@ INCLUDE = os.path.join(HERE, "..", "include")
 # Headers added since the suite began to count the files of include/ live beside it in include_ext/: the same library, the
 # same conventions, the same refusal to build without one of them, and a rebuild trigger of their own (_ext_headers_mtime)
 EXT_HEADERS = ("scat_mano_fit_views.h",)
+# the headers that joined include_ext/ after the first: checked by build() exactly as EXT_HEADERS is
+EXT_HEADERS_MORE = ("scat_mano_fit_seq_views.h",)
 INCLUDE_EXT = os.path.join(HERE, "..", "include_ext")
 
 
@@ -76,7 +78,7 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
     missing = [h for h in PUBLIC_HEADERS if not os.path.exists(os.path.join(INCLUDE, h))]
     if missing:
         raise RuntimeError(f"public headers missing from {os.path.abspath(INCLUDE)}: {missing}")
-    missing = [h for h in EXT_HEADERS if not os.path.exists(os.path.join(INCLUDE_EXT, h))]
+    missing = [h for h in EXT_HEADERS + EXT_HEADERS_MORE if not os.path.exists(os.path.join(INCLUDE_EXT, h))]
     if missing:
         raise RuntimeError(f"public headers missing from {os.path.abspath(INCLUDE_EXT)}: {missing}")
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= _deps_mtime():

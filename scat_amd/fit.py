@@ -63,6 +63,14 @@ one view voted down by the others; the start is triangulated:
     points, valid = fitter.triangulate(kp, cams)       # [B,21,3], [B,21] bool
     uv = fitter.project_views(res, cams)               # [B,C,21,2]
 
+fit_keypoints_views_sequence (include_ext/scat_mano_fit_seq_views.h, csrc/mano_fit_seq_views.hip) is that frame inside
+fit_sequence's track, what a rig's clip needs: one solve per track, a frame that only one camera sees (or none) bridged by
+its neighbours, twist and shape steady over time:
+
+    res = fitter.fit_keypoints_views_sequence(kp, cams, sigma2=10.0,       # SequenceFitResult; kp [S,T,C,21,2] pixels
+                                              smooth=dict(rots=1e2, poses=1e2, betas=1e3, trans=1e6, scale=1e4))
+    uv = fitter.project_views(res, cams)               # [S,T,C,21,2]
+
 There is no CPU fallback: CPU tensors raise ScatError."""
 from __future__ import annotations
 
@@ -92,6 +100,8 @@ FIT_VERTS_HEADER, FIT_POINTS_HEADER, FIT_SEQ_KP_HEADER, FIT_PLANE_HEADER = (
 FIT_SEQ_VERTS_HEADER = os.path.join(HERE, "..", "include", "scat_mano_fit_seq_verts.h")
 # the MANO fit to keypoints in calibrated views; include_ext/ holds the headers added since the suite counts include/'s
 FIT_VIEWS_HEADER = os.path.join(HERE, "..", "include_ext", "scat_mano_fit_views.h")
+# the MANO fit to a track of keypoints in calibrated views
+FIT_SEQ_VIEWS_HEADER = os.path.join(HERE, "..", "include_ext", "scat_mano_fit_seq_views.h")
 VIEWS_MAX_C = 8                # SCAT_FIT_VIEWS_MAX_C
 MAX_F = 4096                   # SCAT_RENDER_MAX_F
 POINTS_MAX_N = 8192            # SCAT_FIT_POINTS_MAX_N
@@ -530,6 +540,24 @@ def mano_fit_views(model, cams, targets2, weights2, joint_map, pose_lo, pose_hi,
                                                      model.V, model.parents_packed, *model.tips, int(iters), int(init),
                                                      float(lambda0), float(w_pose), float(w_beta), float(w_limit), float(sigma2),
                                                      float(z_near), int(free), _stream())
+    return cost, accepted
+
+
+def mano_fit_seq_views(model, cams, targets2, weights2, joint_map, pose_lo, pose_hi, p, iters, init, lambda0, w_pose, w_beta,
+                       w_limit, sigma2, z_near, smooth5, free=ALL_FREE):
+    """scat_mano_fit_seq_views as it is declared: cams [Sc,C,16] with Sc 1 or S, targets2 [S,T,C,21,2], weights2 [S,T,C,21]
+    or None (all ones), joint_map int32 [21] on the device, pose_lo / pose_hi [45] or None, p [S,T,62] (read when init = 0,
+    written), smooth5 = (s_rots, s_poses, s_betas, s_trans, s_scale) -> (cost [S], accepted [S] int32).  The workspace is
+    allocated here, at the size scat_mano_fit_seq_views_ws gives (0 for sizes the launch refuses)."""
+    S, T, C = (int(n) for n in targets2.shape[:3])
+    cost, accepted = _results(S, targets2.device)
+    ns = lib().bind(FIT_SEQ_VIEWS_HEADER)
+    ws, nbytes = _workspace(ns.scat_mano_fit_seq_views_ws, (S, T), targets2.device)
+    ns.scat_mano_fit_seq_views(*_model_args(model), _p(cams), int(cams.shape[0]), _p(targets2), _p(weights2), _p(joint_map),
+                               _p(pose_lo), _p(pose_hi), _p(p), _p(cost), _p(accepted), _p(ws), nbytes, S, T, C, model.V,
+                               model.parents_packed, *model.tips, int(iters), int(init), float(lambda0), float(w_pose),
+                               float(w_beta), float(w_limit), float(sigma2), float(z_near), *(float(v) for v in smooth5),
+                               int(free), _stream())
     return cost, accepted
 
 
@@ -1051,6 +1079,23 @@ class ManoFitter:
         cost, accepted = mano_fit_seq_kp(*args, sm, *frees)
         return KeypointSequenceFitResult(*_groups(p), p[..., 62:65], cost, accepted, p)
 
+    def _views_sequence(self, what, joints2d, cameras, w2):
+        """the checked joints2d [S,T,C,21,2], packed cameras [Sc,C,16] with Sc 1 or S and w2 [S,T,C,21] or None, contiguous"""
+        if not isinstance(cameras, Cameras):
+            raise ScatError(f"{what} needs cameras as a Cameras(R, t, K)")
+        Sc, C = cameras.check(what)
+        _need_gpu(what, joints2d, *cameras, *(() if w2 is None else (w2,)))
+        _check_model(what, self.model, joints2d)
+        S, T = (int(joints2d.shape[0]), int(joints2d.shape[1])) if joints2d.dim() == 5 else (0, 0)
+        if S == 0 or not 1 <= T <= SEQ_MAX_T or tuple(joints2d.shape) != (S, T, C, 21, 2) or joints2d.dtype != torch.float32:
+            raise ScatError(f"{what} needs fp32 joints2d [S,T,{C},21,2] with S >= 1 and T in 1..{SEQ_MAX_T} for {C} cameras, got "
+                            f"{joints2d.dtype} {tuple(joints2d.shape)}")
+        if Sc not in (1, S):
+            raise ScatError(f"{what}: {Sc} rigs for {S} sequences: one rig for all or one per sequence")
+        if cameras.R.device != joints2d.device or (w2 is not None and w2.device != joints2d.device):
+            raise ScatError(f"{what}: the cameras and w2 must be on {joints2d.device}")
+        return joints2d.contiguous(), cameras.packed(), _weights(what, w2, (S, T, C, 21))
+
     def _views(self, what, joints2d, cameras, w2):
         """the checked joints2d [B,C,21,2], packed cameras [Bc,C,16] with Bc 1 or B and w2 [B,C,21] or None, contiguous"""
         if not isinstance(cameras, Cameras):
@@ -1119,25 +1164,93 @@ class ManoFitter:
                                         self._z_near(what, z_near), free)
         return FitResult(*_groups(p), cost, accepted, p)
 
+    def fit_keypoints_views_sequence(self, joints2d, cameras, w2=None, smooth=None, sigma2=0.0, limits=None, w_limit=0.0,
+                                     init=None, free=ALL_FREE, iters=None, z_near=1e-3):
+        """joints2d [S,T,C,21,2] fp32, S tracks of T <= 256 frames seen by C <= 8 calibrated views (cameras: a Cameras with
+        one rig for all tracks or one per track; the rig is fixed along a track) -> SequenceFitResult in the cameras' world
+        frame: joints(), mesh(), project_views(), every track fit's init and MeshRenderer (via flatten(0, 1)) take it as it
+        is.  fit_keypoints_views' problem in every frame (w2 [S,T,C,21] or None; sigma2, limits, w_limit, free, z_near as
+        there, the same for every frame) and fit_sequence's coupling between consecutive frames, solved as one
+        Levenberg-Marquardt per track: one lambda, one accept / reject.
+        smooth: dict(rots=, poses=, betas=, trans=, scale=), the weight d of each group in sum_i d_i (p_t,i - p_t-1,i)^2; a
+        key left out is 0, and all zero decouples the frames.  UNITS: the data term is in pixels squared, summed over up to
+        21 C view-joints per frame, while each smoothness weight multiplies a squared difference in the unknown's own unit:
+        radians squared for rots and poses (the penalty is on the axis-angle numbers), the shape coefficients' for betas,
+        metres squared (the cameras' unit of length) for trans, a log-ratio for scale.  A hand moves by fx s / z pixels per
+        radian and fx / z pixels per metre (about 100 and 1200 for fx = 600, a 0.08 m hand at 0.5 m), so rots = 1e2 counts
+        0.1 rad per frame like one pixel and trans = 1e6 does so for 1 mm per frame; fit_sequence's figures, chosen beside
+        metres squared, are no smoothness at all here.  As in fit_keypoints_views, w_pose = 1e2 counts 0.1 rad like a pixel.
+        A frame whose weights are all zero is legal whatever its finite pixels: it has no data term and is bridged by its
+        neighbours, which is how a hand that no camera sees and a padded clip are passed.  A frame with weight in only one
+        view is legal too: its rows count, which fitting frame by frame cannot offer.
+        init: None for the closed-form start frame by frame (fit_keypoints_views' triangulation and Procrustes; a frame
+        with fewer than 3 triangulated joints takes rots, trans and scale of the frame before it, frame 0 those of the first
+        frame that has a start; rots is made continuous along the track), or p [S,T,62] / a SequenceFitResult,
+        PointSequenceFitResult or KeypointSequenceFitResult (its first 62) to start from (it is not modified).  C = 1 needs
+        an init.  free: bit i clear freezes unknown i in every frame.
+        BEHIND THE CAMERA: a view-joint of positive weight at q.z <= z_near at the start, in any frame, makes the track
+        not fitted, and a trial step with one in any frame is rejected.  Not fitted means cost +inf, accepted 0 and p the
+        start (the scanned closed-form start; zeros when no frame of the track has one); so is a track with a pixel,
+        weight or camera entry that is not finite, or a negative weight, in any frame (p zeros for init None).  The other
+        tracks are not affected."""
+        what = "ManoFitter.fit_keypoints_views_sequence"
+        sm = _smooth(what, smooth)
+        joints2d, cams, w2 = self._views_sequence(what, joints2d, cameras, w2)
+        S, T, C = (int(n) for n in joints2d.shape[:3])
+        if init is None and C < 2:
+            raise ScatError(f"{what}: one view needs a start (init): nothing can be triangulated")
+        lo = hi = None
+        if limits is not None:
+            lo, hi = (torch.as_tensor(t, dtype=torch.float32).to(joints2d.device).contiguous() for t in limits)
+            if tuple(lo.shape) != (POSE,) or tuple(hi.shape) != (POSE,):
+                raise ScatError(f"{what} needs limits (lo[45], hi[45]), got {tuple(lo.shape)}, {tuple(hi.shape)}")
+        p = self._start_sequence(what, init, S, T, joints2d.device)
+        iters = self.iters if iters is None else int(iters)
+        _check_ranges(what, iters, 0 <= int(free) <= ALL_FREE)
+        if min(float(sigma2), float(w_limit)) < 0:
+            raise ScatError(f"{what}: sigma2 and w_limit must not be negative")
+        cost, accepted = mano_fit_seq_views(self.model, cams, joints2d, w2, self._map_on(joints2d.device), lo, hi, p, iters,
+                                            0 if init is not None else 1, self.lambda0, self.w_pose, self.w_beta, w_limit,
+                                            sigma2, self._z_near(what, z_near), sm, free)
+        return SequenceFitResult(*_groups(p), cost, accepted, p)
+
     def triangulate(self, joints2d, cameras, w2=None, z_near=1e-3):
         """joints2d [B,C,21,2], cameras, w2 as in fit_keypoints_views -> (points [B,21,3] fp32, valid [B,21] bool): per joint
         the point nearest to the rays of its views of positive weight (weighted least squares, in fp64).  A joint is valid
         iff at least two of its views have positive weight, the rays are not parallel (closer than about 3 mrad) and the
         point is in front of every contributing camera (q.z > z_near); an invalid joint's point is 0.  A sample with a
-        pixel, weight or camera entry that is not finite, or a negative weight, has no valid joint."""
+        pixel, weight or camera entry that is not finite, or a negative weight, has no valid joint.
+        joints2d [S,T,C,21,2] with w2 [S,T,C,21] and one rig for all tracks or one per track is a clip: every frame is
+        triangulated with its track's rig -> (points [S,T,21,3], valid [S,T,21])."""
         what = "ManoFitter.triangulate"
+        if isinstance(joints2d, torch.Tensor) and joints2d.dim() == 5:
+            joints2d, cams, w2 = self._views_sequence(what, joints2d, cameras, w2)
+            S, T, C = (int(n) for n in joints2d.shape[:3])
+            if cams.shape[0] != 1:   # the rig of a track for each of its frames
+                cams = cams[:, None].expand(S, T, C, 16).reshape(S * T, C, 16).contiguous()
+            points, valid = triangulate_views(cams, joints2d.reshape(S * T, C, 21, 2), None if w2 is None else w2.reshape(S * T, C, 21),
+                                              self._z_near(what, z_near))
+            return points.reshape(S, T, 21, 3), valid.bool().reshape(S, T, 21)
         joints2d, cams, w2 = self._views(what, joints2d, cameras, w2)
         points, valid = triangulate_views(cams, joints2d, w2, self._z_near(what, z_near))
         return points, valid.bool()
 
     def project_views(self, result, cameras):
         """the fitted joints of a result (joints(result), [B,21,3]) in every camera -> [B,C,21,2] pixels; plain torch, no
-        rule about joints behind a camera"""
+        rule about joints behind a camera.  For the result of a track fit ([S,T,21,3]) with one rig for all tracks or one
+        per track -> [S,T,C,21,2]"""
         what = "ManoFitter.project_views"
         if not isinstance(cameras, Cameras):
             raise ScatError(f"{what} needs cameras as a Cameras(R, t, K)")
-        Bc, _ = cameras.check(what)
+        Bc, C = cameras.check(what)
         j = self.joints(result)
+        if j.dim() == 4:
+            S, T = int(j.shape[0]), int(j.shape[1])
+            if Bc not in (1, S) or cameras.R.device != j.device:
+                raise ScatError(f"{what} needs the result of {S} tracks and one rig, or one per track, on {j.device}")
+            rig = Cameras(*(a[:, None].expand(Bc, T, *a.shape[1:]).reshape(Bc * T, *a.shape[1:]) for a in cameras)) if Bc != 1 \
+                else cameras
+            return project_points(j.reshape(S * T, 21, 3), rig).reshape(S, T, C, 21, 2)
         if j.dim() != 3 or Bc not in (1, int(j.shape[0])) or cameras.R.device != j.device:
             raise ScatError(f"{what} needs the result of a batch and one rig, or one per sample, on {j.device}")
         return project_points(j, cameras)

@@ -6,7 +6,8 @@ compare against (SCAT_LIBPATH) and once with this tree's, each in its own proces
 
 The smallest shapes: V = 37, and 778 once per entry point; 6 hands for the joints, keypoint and mesh fits, 2 sequences of 5
 frames (joints, keypoints, meshes and clouds; at V = 37 also of 1 and of 2 frames, the block-tridiagonal walk's smallest), a
-cloud of (3, 257, 37).  5 iterations; the closed-form start and the caller's; one run with a frozen group and one with some
+cloud of (3, 257, 37); 6 hands in 3 calibrated views and 2 tracks of 5 frames in 3 views (at V = 37 also of 1 and of 2
+frames), which a library from before that entry point reports as absent.  5 iterations; the closed-form start and the caller's; one run with a frozen group and one with some
 zero weights.  The plane metric (the mesh fit at three tau, the normals, the assignment, the loop) and the tracks of meshes
 and clouds (a frame without weight, a frame in which nothing matches) come last per V."""
 import hashlib
@@ -30,11 +31,13 @@ def main():
     import _fit_seq_cases as SC
     import _fit_seq_kp_cases as QC
     import _fit_seq_verts_cases as GC
+    import _fit_seq_views_cases as XC
     import _fit_verts_cases as VC
+    import _fit_views_cases as WC
     from _fit_cases import JOINT_MAP, host_model
     from scat_amd import synth
     from scat_amd._lib import lib
-    from scat_amd.fit import (ManoFitter, Topology, free_mask, mano_cloud_assign_plane, mano_fit_verts_metric, mano_joints_jac,
+    from scat_amd.fit import (Cameras, ManoFitter, Topology, free_mask, mano_cloud_assign_plane, mano_fit_verts_metric, mano_joints_jac,
                               mano_verts_jac, mesh_normals)
 
     lib().scat_check_device()
@@ -110,6 +113,40 @@ def main():
                 show(f"v{V}.seq.t{T}", fitter.fit_sequence(SC.track(25, 2, T, V)[1].to(dev), smooth=SC.SMOOTH))
                 _, R3, R2 = QC.truth(25, 2, T, V)
                 show(f"v{V}.seqkp.t{T}", seqkp(joints3d=R3.to(dev), joints2d=R2.to(dev), w2=q2[:, :T].contiguous(), smooth=QC.SMOOTH))
+
+        # keypoints in calibrated views: a rig per hand, the triangulated start and the caller's; then tracks of them
+        def rig(c):
+            c = c.to(dev)
+            return Cameras(c[:, :, :9].reshape(c.shape[0], -1, 3, 3).contiguous(), c[:, :, 9:12].contiguous(), c[:, :, 12:16].contiguous())
+
+        vf = ManoFitter(fitter.model, joint_map=JOINT_MAP, iters=ITERS, w_pose=1e-2, w_beta=1e-2)
+        U2, ucams = WC.truth(V, 6, 3, True)[2].to(dev), rig(WC.truth(V, 6, 3, True)[3])
+        near_w = WC.near_start(V, 6, 3, True).float().to(dev)
+        box = torch.full((45,), WC.BOX)
+        wu = torch.ones(6, 3, 21, device=dev)
+        wu[:, 0, ::4] = 0.0
+        wu[:, 1, 1] = 0.5
+        show(f"v{V}.triangulate", vf.triangulate(U2, ucams, w2=wu))
+        show(f"v{V}.views", vf.fit_keypoints_views(U2, ucams))
+        show(f"v{V}.views.init", vf.fit_keypoints_views(U2, ucams, init=near_w, sigma2=WC.SIGMA2, limits=(-box, box), w_limit=WC.W_LIMIT))
+        show(f"v{V}.views.frozen", vf.fit_keypoints_views(U2, ucams, init=near_w, free=frozen))
+        show(f"v{V}.views.weights", vf.fit_keypoints_views(U2, ucams, w2=wu, sigma2=WC.SIGMA2))
+        try:
+            sm = dict(zip(("rots", "poses", "betas", "trans", "scale"), XC.SMOOTH))
+            seqw = vf.fit_keypoints_views_sequence
+            for T in (1, 2, 5) if V == 37 else (5,):
+                Y2, ycams = XC.truth(V, 2, T, 3)[2].to(dev), rig(XC.truth(V, 2, T, 3)[3])
+                show(f"v{V}.seqviews.t{T}", seqw(Y2, ycams, smooth=sm))
+            near_y = XC.near_start(V, 2, 5, 3).float().to(dev)
+            wy = torch.ones(2, 5, 3, 21, device=dev)
+            wy[:, 2, 1:] = 0.0                                       # a frame that one camera sees
+            wy[0, 3] = 0.0                                           # and one that none sees
+            show(f"v{V}.seqviews.init", seqw(Y2, ycams, smooth=sm, init=near_y, sigma2=XC.SIGMA2, limits=(-box, box), w_limit=XC.W_LIMIT))
+            show(f"v{V}.seqviews.frozen", seqw(Y2, ycams, smooth=sm, init=near_y, free=frozen))
+            show(f"v{V}.seqviews.weights", seqw(Y2, ycams, w2=wy, smooth=sm, sigma2=XC.SIGMA2))
+            show(f"v{V}.seqviews.decoupled", seqw(Y2, ycams))
+        except AttributeError as e:      # a library from before scat_mano_fit_seq_views
+            print(f"v{V}.seqviews absent: {str(e).split(', which')[0].split('/')[-1]}")
 
         show(f"v{V}.verts_jac", mano_verts_jac(fitter.model, P[:, 0:3], P[:, 3:48], P[:, 48:58]))
         show(f"v{V}.verts", fitter.fit_vertices(Tv))
